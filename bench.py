@@ -13,11 +13,17 @@ reference src/perphil/solvers/solver.py:65-69 under experiments/petsc_profiling_
 that one-off cost is reported beside the step as `config.setup_ms` and `config.cold_step_ms`).
 
     python bench.py --gpus 1 --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus 1 --steps K --warmup W --full   (everything below besides the headline)
+    python bench.py ... --dump-outputs DIR                 (the last timed step's result as .npy files)
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline` (the SpMV kernel of the
-block solves on the stencil-ELL operator format, HIP events per launch on the solver's stream, algorithmic
-bytes 8 S nrows + 16 nrows; the CSR kernel's figures - 12 nnz + 20 nrows - beside it under `roofline.csr`)
-and `cpu_baseline` (oracle/dpp_cpu.c, the C/OpenMP restatement of the same step, on the host's cores).
+A plain run sets up, runs W warm-up steps and K timed steps, and prints ONE JSON line (rank 0) with the
+driver's contract fields (`value` = DoF/s over the K steps, `ms_per_step`) and the step's `config`.
+With --full the same line also carries `roofline` (the SpMV kernel of the block solves on the stencil-ELL
+operator format, HIP events per launch on the solver's stream, algorithmic bytes 8 S nrows + 16 nrows; the
+CSR kernel's figures - 12 nnz + 20 nrows - beside it under `roofline.csr`), `cpu_baseline` and `parity`
+(oracle/dpp_cpu.c, the C/OpenMP restatement of the same step, on the host's cores), `config.api` (the public
+API's wall clock), `config.comm` (N > 1) and `configs` (the other single-GPU BASELINE configurations); these
+take untimed steps and runs of their own after the timed ones.  Without --full they are null or absent.
 """
 import argparse
 import json
@@ -32,6 +38,25 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
+
+
+DUMP_SAMPLE = 1 << 21   # nodes per field written by --dump-outputs (float64: 2 x 16 MB at most)
+DUMP_SEED = 20261016
+
+
+def dump_outputs(path, x, info):
+    """--dump-outputs: what a caller of the timed step receives from its last run - the solution of both pressure
+    fields (field-major x = [p1, p2], float64; above DUMP_SAMPLE nodes a fixed sample of DUMP_SAMPLE node ids drawn
+    with DUMP_SEED, in ascending order, the same for every run of the same size) and the solve's report (outer
+    iterations, inner CG iterations, final residual, right-hand-side norm)."""
+    os.makedirs(path, exist_ok=True)
+    n = x.size // 2
+    idx = (np.arange(n) if n <= DUMP_SAMPLE else
+           np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False)))
+    for f, name in enumerate(("p1", "p2")):
+        np.save(os.path.join(path, f"solution_{name}.npy"), np.ascontiguousarray(x[f * n:(f + 1) * n][idx], dtype=np.float64))
+    np.save(os.path.join(path, "solve_info.npy"),
+            np.array([info.iterations, info.inner_iterations, info.resnorm, info.rhs_norm], dtype=np.float64))
 
 
 def picard_cfg(_ffi, inner_rtol=1e-10, smooth=2, reduction=0.0, inner_norm=0, inner_max_it=50000):
@@ -419,7 +444,16 @@ def main():
                          "metric; 5: P1 Kuhn tetrahedra, k1/k2 = 1e4, GMRES + field-split - on --gpus N slabs either way")
     ap.add_argument("--no-configs", action="store_true",
                     help="omit the timed runs of the other single-GPU BASELINE configurations (1, 2, 3, 5; 'configs' in the line)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything besides the headline: roofline and "
+                         "alternative operator formats, communication split (N > 1), public-API wall clock, CPU baseline "
+                         "with parity against it, the other BASELINE configurations (the --no-* / --skip-* options "
+                         "trim this part)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result to DIR/*.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started like the 1-GPU run (`python bench.py --gpus N`): launch the ranks as a CHILD process - nothing in this
@@ -538,9 +572,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     tm = ctx.timers()
-    # the timed steps' solution, for the parity check against the port below (272 MB at 256^3; outside the timed region)
-    x_gpu = ctx.solution() if (world == 1 and not args.no_cpu_baseline) else None
+    # the timed steps' solution, for --dump-outputs and the parity check against the port below (272 MB at 256^3; outside
+    # the timed region)
+    x_gpu = ctx.solution() if (world == 1 and (args.dump_outputs or (args.full and not args.no_cpu_baseline))) else None
     info_timed = info
+    if args.dump_outputs:
+        x_all = x_gpu if world == 1 else solver.gather_solution()     # (slabs: collective, every rank takes part)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, x_all, info)
+        del x_all
 
     # ---- roofline of the dominant kernel: one more (untimed) step with an event pair around every
     # SpMV launch on the solver's stream; bytes are algorithmic (stencil-ELL: 8 S nrows + 16 nrows per
@@ -573,8 +613,11 @@ def main():
                 "achieved": round(fa, 1), "frac": round(fa / HBM_PEAK_GBS, 4)}
 
     sell = not any(kv.split("=")[0] == "op_format" and float(kv.split("=")[1]) == 0 for kv in args.set)
-    tr, launches, ms, byts = instrumented_step()
-    achieved = (byts / 1e9) / (ms / 1e3) if ms > 0 else 0.0
+    if args.full:
+        tr, launches, ms, byts = instrumented_step()
+        achieved = (byts / 1e9) / (ms / 1e3) if ms > 0 else 0.0
+    else:
+        tr = tm                  # a plain run: the format facts of the line's config from the timed steps' own report
     sym = bool(ctx.timers().get("symmetric_storage", False))   # what the last assembly actually stored
     SF = 15 if c5 else 27        # stencil: 27-point (Q1 hexahedra) / 15-point (P1 Kuhn tetrahedra)
     S = SF // 2 + 1 if sym else SF   # stored slots per row: diagonal + upper half of the stencil, or all of it
@@ -593,120 +636,121 @@ def main():
     cls_bytes = 2.0 * 4.0 / (N + 1) if zconst else 2.0
     sell_bytes = (cls_bytes if dicton else 8.0 * S) * ctx.n + 16.0 * ctx.n
     csr_bytes = 12.0 * ctx.nnzb + 20.0 * ctx.n
-    # HBM traffic of the same kernel mix from rocprofv3 PMC passes (FETCH_SIZE x2 on gfx950 + WRITE_SIZE, KB), taken
-    # offline with tools/pmc_summarize.py and committed under profiles/ (PMC cannot be sampled in-process).  The
-    # file is stamped with the kernel and the launch count it was taken on: anything else reports null.
-    traffic = None
-    pmc_file = os.path.join(ROOT, "profiles", "r04_pmc_spmv_dict_bench256.json" if dicton else "r03_pmc_spmv_bench256.json")
-    if os.path.exists(pmc_file) and N == 256 and world == 1 and sell and not c5:
-        try:
-            with open(pmc_file) as f:
-                pmc = json.load(f)
-            if (int(pmc.get("launches_per_step", -1)) == int(launches) and pmc.get("kernel") in ("k_spmv_sell", "k_spmv")
-                    and bool(pmc.get("symmetric", False)) == bool(sym) and bool(pmc.get("dictionary", False)) == dicton):
-                traffic = pmc.get("traffic_bytes_per_launch")
-        except (OSError, ValueError):
-            traffic = None
-    roofline = {
-        "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-        "kernel": ((f"k_spmv_sell<tet,mode,2,sym,DICT> (15-point stencil-ELL SpMV on row dictionaries: {dict_classes} distinct rows of "
-                    "A11 in LDS, a 2-byte class per row instead of the 8 stored values; field-split block solves; the monolithic "
-                    "GMRES products run k_spmv_wide on the field-major CSR and are not in this figure)") if (dicton and c5) else
-                   (f"k_spmv_dict_walk<mode> (stencil-ELL SpMV on row dictionaries: {dict_classes} distinct rows of A11 in LDS, a "
-                    "2-byte class per row instead of the 14 stored values" + (" - read on four planes only: the classes of an in-plane "
-                    "position are constant on the interior planes" if zconst else "") + ", x window of three planes in registers; operators "
-                    "below 1 M rows - the coarse multigrid levels - k_spmv_sell on their stored values; all multigrid "
-                    "levels of one step)")
-                   if dicton else
-                   (f"k_spmv_sell<kind,mode,2,{'sym' if sym else 'full'}> (stencil-ELL SpMV, "
-                    + ("symmetric storage: 14 of 27 slot arrays, every value serves two rows, " if sym else "")
-                    + "8 B per stored entry, all multigrid levels of one step)")
-                   if sell else "k_spmv_wide<8,*,2> (aligned-wide CSR-vector SpMV, all multigrid levels of one step)"),
-        "format": (("row dictionary over " if dicton else "") + ("stencil-ELL (symmetric)" if sym else "stencil-ELL")) if sell else "CSR",
-        "dictionary": {"operators": dict_ops, "classes_A11": dict_classes, "classes_constant_along_z": zconst} if sell else None,
-        "launches_per_step": int(launches), "avg_launch_us": round(1e3 * ms / max(launches, 1), 2),
-        "algorithmic_bytes_per_launch": round(byts / max(launches, 1), 0),
-        "fine_level": fine_block(sell_bytes if sell else csr_bytes),
-        "fine_level_in_solver": in_solver(tr),
-    }
-    if dicton and extra_records:
-        # the same step with the products on the STORED values (symmetric stencil-ELL, the dominant kernel of rounds 2-3
-        # and the path of every mesh whose rows do not repeat): untimed, for the record
-        ctx.set_option("sell_dict", 0)
-        step()
-        tv, lv, msv, bv = instrumented_step()
-        t0v = time.perf_counter()
-        step()
-        ctx.synchronize()
-        stored_ms = 1e3 * (time.perf_counter() - t0v)
-        av = (bv / 1e9) / (msv / 1e3) if msv > 0 else 0.0
-        stored_bytes = 8.0 * S * ctx.n + 16.0 * ctx.n
-        roofline["stored_values"] = {"kernel": "k_spmv_sell<kind,mode,2,sym> (14 stored slot arrays, every value serves two rows)",
-                                     "achieved": round(av, 1), "frac": round(av / HBM_PEAK_GBS, 4), "launches_per_step": int(lv),
-                                     "algorithmic_bytes_per_launch": round(bv / max(lv, 1), 0), "ms_per_step": round(stored_ms, 3),
-                                     "fine_level": fine_block(stored_bytes), "fine_level_in_solver": in_solver(tv)}
-        ctx.set_option("sell_dict", 1)
-        step()                                   # (the dictionaries are rebuilt by the next assembly)
-    if sell and sym and extra_records:
-        # the same step on full (27-slot) stencil-ELL storage: untimed, for the record
-        ctx.set_option("sell_sym", 0)
-        step()
-        tf, lf, msf, bf = instrumented_step()
-        t0f = time.perf_counter()
-        step()
-        ctx.synchronize()
-        full_ms = 1e3 * (time.perf_counter() - t0f)
-        af = (bf / 1e9) / (msf / 1e3) if msf > 0 else 0.0
-        full_bytes = 8.0 * SF * ctx.n + 16.0 * ctx.n
-        roofline["full_storage"] = {"kernel": "k_spmv_sell<kind,mode,2,full> (all 27 slot arrays)", "achieved": round(af, 1),
-                                    "frac": round(af / HBM_PEAK_GBS, 4), "launches_per_step": int(lf),
-                                    "algorithmic_bytes_per_launch": round(bf / max(lf, 1), 0), "ms_per_step": round(full_ms, 3),
-                                    "fine_level": fine_block(full_bytes), "fine_level_in_solver": in_solver(tf)}
-        ctx.set_option("sell_sym", 1)
-    if sell and extra_records:
-        # the same step on the CSR operator format (the north-star's "CSR SpMV inner loop"): untimed, for the record
-        ctx.set_option("op_format", 0)
-        step()                                   # re-assembles into CSR arrays, rebuilds the level operators
-        tc, lc, msc, bc = instrumented_step()
-        t0c = time.perf_counter()
-        step()
-        ctx.synchronize()
-        csr_step_ms = 1e3 * (time.perf_counter() - t0c)
-        ac = (bc / 1e9) / (msc / 1e3) if msc > 0 else 0.0
-        roofline["csr"] = {"kernel": "k_spmv_wide<8,*,2> (aligned-wide CSR-vector SpMV)", "achieved": round(ac, 1),
-                           "frac": round(ac / HBM_PEAK_GBS, 4), "launches_per_step": int(lc),
-                           "algorithmic_bytes_per_launch": round(bc / max(lc, 1), 0), "ms_per_step": round(csr_step_ms, 3),
-                           "fine_level": fine_block(csr_bytes), "fine_level_in_solver": in_solver(tc)}
-        ctx.set_option("op_format", 1)
     cs = ctx.comm_stats()
-    # communication split of one more (untimed) step: every halo exchange / all-reduce bracketed by an event pair on the
-    # stream it runs on (RCCL transport; callback transports: host clock inside the callback), so that a measured scaling
-    # curve can be read: comm_ms (exchange, all-reduce) beside the step's wall time taken the same way
-    comm = None
-    if world > 1:
-        ctx.set_option("time_comm", 1)
-        fence()
-        tq = time.perf_counter()
-        step()
-        ctx.synchronize()
-        step_ms_timed = 1e3 * (time.perf_counter() - tq)
-        ct = ctx.comm_times()
-        ctx.set_option("time_comm", 0)
-        vals = [ct["halo_ms"], ct["allreduce_ms"], step_ms_timed]
-        tv = torch.tensor(vals, dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
-        dist.all_reduce(tv, op=dist.ReduceOp.MAX)
-        halo_ms, ar_ms, step_ms_timed = (float(v) for v in tv.tolist())
-        overlapped = args.halo_overlap == 1 and transport == "rccl"
-        comm = {"halo_ms": round(halo_ms, 3), "allreduce_ms": round(ar_ms, 3),
-                "halo_exchanges_timed": ct["halo_timed"], "allreduces_timed": ct["allreduce_timed"],
-                "step_ms_with_comm_timers": round(step_ms_timed, 3),
-                "kernel_ms": round(step_ms_timed - ar_ms - (0.0 if overlapped else halo_ms), 3),
-                "what": "max over ranks, one extra untimed step; rccl transport: device time between HIP events around each "
-                        "grouped ncclSend/ncclRecv and each ncclAllReduce (an exchange overlapped with interior rows counts "
-                        "its full duration on the communication stream and is NOT subtracted in kernel_ms); callback "
-                        "transports: host time inside the callback; kernel_ms = the step's wall time minus the serial "
-                        "communication = kernels + launch gaps + host round trips"}
+    roofline = comm = None
+    if args.full:
+        # HBM traffic of the same kernel mix from rocprofv3 PMC passes (FETCH_SIZE x2 on gfx950 + WRITE_SIZE, KB), taken
+        # offline with tools/pmc_summarize.py and committed under profiles/ (PMC cannot be sampled in-process).  The
+        # file is stamped with the kernel and the launch count it was taken on: anything else reports null.
+        traffic = None
+        pmc_file = os.path.join(ROOT, "profiles", "r04_pmc_spmv_dict_bench256.json" if dicton else "r03_pmc_spmv_bench256.json")
+        if os.path.exists(pmc_file) and N == 256 and world == 1 and sell and not c5:
+            try:
+                with open(pmc_file) as f:
+                    pmc = json.load(f)
+                if (int(pmc.get("launches_per_step", -1)) == int(launches) and pmc.get("kernel") in ("k_spmv_sell", "k_spmv")
+                        and bool(pmc.get("symmetric", False)) == bool(sym) and bool(pmc.get("dictionary", False)) == dicton):
+                    traffic = pmc.get("traffic_bytes_per_launch")
+            except (OSError, ValueError):
+                traffic = None
+        roofline = {
+            "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+            "kernel": ((f"k_spmv_sell<tet,mode,2,sym,DICT> (15-point stencil-ELL SpMV on row dictionaries: {dict_classes} distinct rows of "
+                        "A11 in LDS, a 2-byte class per row instead of the 8 stored values; field-split block solves; the monolithic "
+                        "GMRES products run k_spmv_wide on the field-major CSR and are not in this figure)") if (dicton and c5) else
+                       (f"k_spmv_dict_walk<mode> (stencil-ELL SpMV on row dictionaries: {dict_classes} distinct rows of A11 in LDS, a "
+                        "2-byte class per row instead of the 14 stored values" + (" - read on four planes only: the classes of an in-plane "
+                        "position are constant on the interior planes" if zconst else "") + ", x window of three planes in registers; operators "
+                        "below 1 M rows - the coarse multigrid levels - k_spmv_sell on their stored values; all multigrid "
+                        "levels of one step)")
+                       if dicton else
+                       (f"k_spmv_sell<kind,mode,2,{'sym' if sym else 'full'}> (stencil-ELL SpMV, "
+                        + ("symmetric storage: 14 of 27 slot arrays, every value serves two rows, " if sym else "")
+                        + "8 B per stored entry, all multigrid levels of one step)")
+                       if sell else "k_spmv_wide<8,*,2> (aligned-wide CSR-vector SpMV, all multigrid levels of one step)"),
+            "format": (("row dictionary over " if dicton else "") + ("stencil-ELL (symmetric)" if sym else "stencil-ELL")) if sell else "CSR",
+            "dictionary": {"operators": dict_ops, "classes_A11": dict_classes, "classes_constant_along_z": zconst} if sell else None,
+            "launches_per_step": int(launches), "avg_launch_us": round(1e3 * ms / max(launches, 1), 2),
+            "algorithmic_bytes_per_launch": round(byts / max(launches, 1), 0),
+            "fine_level": fine_block(sell_bytes if sell else csr_bytes),
+            "fine_level_in_solver": in_solver(tr),
+        }
+        if dicton and extra_records:
+            # the same step with the products on the STORED values (symmetric stencil-ELL, the dominant kernel of rounds 2-3
+            # and the path of every mesh whose rows do not repeat): untimed, for the record
+            ctx.set_option("sell_dict", 0)
+            step()
+            tv, lv, msv, bv = instrumented_step()
+            t0v = time.perf_counter()
+            step()
+            ctx.synchronize()
+            stored_ms = 1e3 * (time.perf_counter() - t0v)
+            av = (bv / 1e9) / (msv / 1e3) if msv > 0 else 0.0
+            stored_bytes = 8.0 * S * ctx.n + 16.0 * ctx.n
+            roofline["stored_values"] = {"kernel": "k_spmv_sell<kind,mode,2,sym> (14 stored slot arrays, every value serves two rows)",
+                                         "achieved": round(av, 1), "frac": round(av / HBM_PEAK_GBS, 4), "launches_per_step": int(lv),
+                                         "algorithmic_bytes_per_launch": round(bv / max(lv, 1), 0), "ms_per_step": round(stored_ms, 3),
+                                         "fine_level": fine_block(stored_bytes), "fine_level_in_solver": in_solver(tv)}
+            ctx.set_option("sell_dict", 1)
+            step()                                   # (the dictionaries are rebuilt by the next assembly)
+        if sell and sym and extra_records:
+            # the same step on full (27-slot) stencil-ELL storage: untimed, for the record
+            ctx.set_option("sell_sym", 0)
+            step()
+            tf, lf, msf, bf = instrumented_step()
+            t0f = time.perf_counter()
+            step()
+            ctx.synchronize()
+            full_ms = 1e3 * (time.perf_counter() - t0f)
+            af = (bf / 1e9) / (msf / 1e3) if msf > 0 else 0.0
+            full_bytes = 8.0 * SF * ctx.n + 16.0 * ctx.n
+            roofline["full_storage"] = {"kernel": "k_spmv_sell<kind,mode,2,full> (all 27 slot arrays)", "achieved": round(af, 1),
+                                        "frac": round(af / HBM_PEAK_GBS, 4), "launches_per_step": int(lf),
+                                        "algorithmic_bytes_per_launch": round(bf / max(lf, 1), 0), "ms_per_step": round(full_ms, 3),
+                                        "fine_level": fine_block(full_bytes), "fine_level_in_solver": in_solver(tf)}
+            ctx.set_option("sell_sym", 1)
+        if sell and extra_records:
+            # the same step on the CSR operator format (the north-star's "CSR SpMV inner loop"): untimed, for the record
+            ctx.set_option("op_format", 0)
+            step()                                   # re-assembles into CSR arrays, rebuilds the level operators
+            tc, lc, msc, bc = instrumented_step()
+            t0c = time.perf_counter()
+            step()
+            ctx.synchronize()
+            csr_step_ms = 1e3 * (time.perf_counter() - t0c)
+            ac = (bc / 1e9) / (msc / 1e3) if msc > 0 else 0.0
+            roofline["csr"] = {"kernel": "k_spmv_wide<8,*,2> (aligned-wide CSR-vector SpMV)", "achieved": round(ac, 1),
+                               "frac": round(ac / HBM_PEAK_GBS, 4), "launches_per_step": int(lc),
+                               "algorithmic_bytes_per_launch": round(bc / max(lc, 1), 0), "ms_per_step": round(csr_step_ms, 3),
+                               "fine_level": fine_block(csr_bytes), "fine_level_in_solver": in_solver(tc)}
+            ctx.set_option("op_format", 1)
+        # communication split of one more (untimed) step: every halo exchange / all-reduce bracketed by an event pair on the
+        # stream it runs on (RCCL transport; callback transports: host clock inside the callback), so that a measured scaling
+        # curve can be read: comm_ms (exchange, all-reduce) beside the step's wall time taken the same way
+        if world > 1:
+            ctx.set_option("time_comm", 1)
+            fence()
+            tq = time.perf_counter()
+            step()
+            ctx.synchronize()
+            step_ms_timed = 1e3 * (time.perf_counter() - tq)
+            ct = ctx.comm_times()
+            ctx.set_option("time_comm", 0)
+            vals = [ct["halo_ms"], ct["allreduce_ms"], step_ms_timed]
+            tv = torch.tensor(vals, dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
+            dist.all_reduce(tv, op=dist.ReduceOp.MAX)
+            halo_ms, ar_ms, step_ms_timed = (float(v) for v in tv.tolist())
+            overlapped = args.halo_overlap == 1 and transport == "rccl"
+            comm = {"halo_ms": round(halo_ms, 3), "allreduce_ms": round(ar_ms, 3),
+                    "halo_exchanges_timed": ct["halo_timed"], "allreduces_timed": ct["allreduce_timed"],
+                    "step_ms_with_comm_timers": round(step_ms_timed, 3),
+                    "kernel_ms": round(step_ms_timed - ar_ms - (0.0 if overlapped else halo_ms), 3),
+                    "what": "max over ranks, one extra untimed step; rccl transport: device time between HIP events around each "
+                            "grouped ncclSend/ncclRecv and each ncclAllReduce (an exchange overlapped with interior rows counts "
+                            "its full duration on the communication stream and is NOT subtracted in kernel_ms); callback "
+                            "transports: host time inside the callback; kernel_ms = the step's wall time minus the serial "
+                            "communication = kernels + launch gaps + host round trips"}
 
     out = {
         "metric": ("DoF/s (assemble+solve), 3D UnitCube P1 (Kuhn tetrahedra) DPP, k1/k2 = 1e4, GMRES + field-split" if c5 else
@@ -760,14 +804,14 @@ def main():
         },
         "roofline": roofline,
     }
-    if rank == 0 and world == 1 and not args.no_api_wall and not c5:
+    if rank == 0 and world == 1 and args.full and not args.no_api_wall and not c5:
         out["config"]["api"] = api_wall(N, k1, k2, beta, mu)
     parity_failed = False
     if c5:
         if rank == 0:
             out["cpu_baseline"] = None
             out["parity_vs_port"] = None
-    elif rank == 0 and not args.no_cpu_baseline and world == 1:
+    elif rank == 0 and args.full and not args.no_cpu_baseline and world == 1:
         keep = {}
         out["cpu_baseline"] = cpu_baseline(min(args.cpu_sample_n, N), k1, k2, beta, mu, args.smooth, args.inner_reduction,
                                            args.inner_rtol, args.cpu_threads, args.inner_norm, keep)
@@ -789,7 +833,7 @@ def main():
     elif rank == 0:
         out["cpu_baseline"] = None
         out["parity_vs_port"] = None
-    if rank == 0 and world == 1 and not args.no_configs and not c5 and N == 256:
+    if rank == 0 and world == 1 and args.full and not args.no_configs and not c5 and N == 256:
         # the other BASELINE configurations that fit one GPU, each timed and checked (after the headline: own contexts)
         ctx.close()
         cfgs = bench_configs(_ffi, device, not args.no_cpu_baseline, args.cpu_threads if args.cpu_threads > 0 else host_cores())

@@ -161,7 +161,7 @@ def test_bench_gpus_2_starts_its_own_ranks(config):
     env = dict(os.environ, PERPHIL_DIST_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cells", "16", "--steps", "1",
-                        "--warmup", "1", "--no-cpu-baseline", "--skip-fine-bench", "--skip-csr", "--config", str(config)],
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--skip-fine-bench", "--skip-csr", "--config", str(config)],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-2000:])
@@ -177,3 +177,37 @@ def test_bench_gpus_2_starts_its_own_ranks(config):
         assert "tetrahedra" in c["workload"] and c["gmres_iterations"] == 4 and c["cells"] == 6 * 16 ** 3
     else:
         assert c["picard_sweeps"] > 0
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_result(tmp_path):
+    """`python bench.py --gpus 1` without --full: the line carries the headline fields for exactly --steps timed steps and
+    none of the extra measurements; --dump-outputs writes the last timed step's solution and solve report, the same from
+    run to run (same arguments -> same inputs)."""
+    import json
+
+    import numpy as np
+
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--cells", "16", "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(d)], cwd=ROOT, capture_output=True, text=True, timeout=200)
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-2000:])
+        out = json.loads(lines[0])
+        runs.append((out, {f: np.load(d / f) for f in ("solution_p1.npy", "solution_p2.npy", "solve_info.npy")}))
+    for out, arrs in runs:
+        c = out["config"]
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["unit"] == "DoF/s" and out["higher_is_better"] is True
+        assert out["dtype"] == "f64" and out["value"] > 0 and out["ms_per_step"] > 0
+        assert abs(out["value"] * out["ms_per_step"] / 1e3 - c["dofs"]) <= 1e-6 * c["dofs"]
+        assert out["roofline"] is None and out["cpu_baseline"] is None and "configs" not in out and "api" not in c
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        assert arrs["solution_p1.npy"].shape == arrs["solution_p2.npy"].shape == (17 ** 3,) and 2 * 17 ** 3 == c["dofs"]
+        sweeps, inner, res, rhs = arrs["solve_info.npy"]
+        assert (sweeps, inner, res, rhs) == (c["picard_sweeps"], c["inner_cg_iterations"], c["final_residual"], c["rhs_norm"])
+    (_, a), (_, b) = runs
+    assert np.array_equal(a["solve_info.npy"][:2], b["solve_info.npy"][:2])
+    for f in ("solution_p1.npy", "solution_p2.npy"):
+        assert np.isfinite(a[f]).all()
+        np.testing.assert_allclose(b[f], a[f], rtol=0, atol=1e-12 * np.abs(a[f]).max())

@@ -1,7 +1,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r3final; rm -rf $O; mkdir -p $O
 timeout -k 5 700 python3 -m pytest tests -m gpu -x -q --durations=10 > $O/pytest.log 2>&1; tail -16 $O/pytest.log
-timeout -k 5 300 python3 bench.py > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err; python3 - <<PY
+timeout -k 5 300 python3 bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err; python3 - <<PY
 import json
 d=json.load(open('$O/bench.json'))
 print('ms_per_step', d['ms_per_step'], 'value', d['value'], 'context', d['config']['context_ms'], 'setup', d['config']['setup_ms'], 'cold', d['config']['cold_step_ms'], 'asm', d['config']['assemble_ms'], 'solve', d['config']['solve_ms'])

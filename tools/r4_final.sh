@@ -1,9 +1,9 @@
 # round-4 evidence pass: default bench line, kernel stats + gaps, PMC traffic of the SpMV and assembly kernels
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r4final; rm -rf $O; mkdir -p $O
-timeout -k 5 400 python3 bench.py > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
-B="bench.py --cells 256 --steps 1 --warmup 1 --no-cpu-baseline --no-api-wall --skip-fine-bench --skip-csr --no-configs"
-timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o ks -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-api-wall --skip-fine-bench --skip-csr --no-configs > $O/under_rocprof.json 2> $O/ks.err || { tail -5 $O/ks.err; exit 1; }
+timeout -k 5 400 python3 bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
+B="bench.py --full --cells 256 --steps 1 --warmup 1 --no-cpu-baseline --no-api-wall --skip-fine-bench --skip-csr --no-configs"
+timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o ks -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-api-wall --skip-fine-bench --skip-csr --no-configs > $O/under_rocprof.json 2> $O/ks.err || { tail -5 $O/ks.err; exit 1; }
 cp $(find $O/ks -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv
 python3 tools/gap_hist.py $O/ks > $O/gaps256.txt
 rm -rf $O/ks

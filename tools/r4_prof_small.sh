@@ -2,7 +2,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for N in 64 128; do
 O=gpurun_out/prof4s_$N; rm -rf $O; mkdir -p $O
-timeout -k 5 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o ks -- python3 bench.py --cells $N --steps 10 --warmup 2 --no-cpu-baseline --no-api-wall --skip-fine-bench --skip-csr --no-configs "$@" > $O/line.json 2> $O/ks.err || { tail -5 $O/ks.err; exit 1; }
+timeout -k 5 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o ks -- python3 bench.py --full --cells $N --steps 10 --warmup 2 --no-cpu-baseline --no-api-wall --skip-fine-bench --skip-csr --no-configs "$@" > $O/line.json 2> $O/ks.err || { tail -5 $O/ks.err; exit 1; }
 cp $(find $O/ks -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv
 python3 tools/gap_hist.py $O/ks > $O/gaps.txt
 rm -rf $O/ks
