@@ -137,6 +137,10 @@ int pph_get_coords(pph_ctx* ctx, double* coords_host /* [n_nodes][dim] */);
  * values (evaluated by the caller, e.g. from the manufactured solution,
  * src/perphil/utils/manufactured_solutions.py:39-51,87-88).  Replaces earlier data of `field`. */
 int pph_set_dirichlet(pph_ctx* ctx, int field, const int64_t* nodes, const double* vals, int64_t count);
+/* the same from DEVICE arrays (nodes, vals: `count` entries in memory of the context's device, e.g. torch tensors): the
+ * node range is checked on the device, then the mask / value scatter of pph_set_dirichlet runs on the context stream.
+ * Returns once the context stream has finished with both arrays. */
+int pph_set_dirichlet_device(pph_ctx* ctx, int field, const int64_t* nodes, const double* vals, int64_t count);
 
 /* ---- assembly -----------------------------------------------------------------------------
  * replaces: dpp_form() (reference src/perphil/forms/dpp.py:95-132) + the TSFC element kernel /
@@ -158,6 +162,12 @@ int pph_solve(pph_ctx* ctx, const pph_solver_cfg* cfg, double* x_host, pph_solve
 /* same solve, result left on the device (timing without the PCIe copy); fetch with pph_get_solution */
 int pph_solve_device(pph_ctx* ctx, const pph_solver_cfg* cfg, pph_solve_info* info, double* hist, int hist_cap);
 int pph_get_solution(pph_ctx* ctx, double* x_host /* len 2n */);
+/* Device-resident results (no reference counterpart: Firedrake's Function lives in host memory).  The context's HIP stream
+ * (a hipStream_t, non-blocking) for ordering a caller's own device work against the library's in both directions; and a copy
+ * of the current solution (field-major, count = 2n local) into a CALLER-OWNED device buffer, enqueued on that stream and not
+ * waited for.  The library never frees nor keeps dst. */
+int pph_get_stream(pph_ctx* ctx, void** stream);
+int pph_copy_solution_device(pph_ctx* ctx, double* dst, int64_t count);
 /* Page-locked host memory for the x_host / result arrays above (no reference counterpart: PETSc's Vec lives in host memory
  * already).  A copy into pageable memory is staged by the HIP runtime and pays the first touch of a fresh array's pages; the
  * Python host side keeps a small pool of pinned result buffers (perphil_amd/_ffi.py: Context.solution).  Freed with
@@ -202,12 +212,30 @@ int pph_error_norms_mms(pph_ctx* ctx, int field, const double* nodal_host, doubl
 int pph_quadrature_points(pph_ctx* ctx, int nq, int64_t cell_begin, int64_t cell_count, double* xq_host);
 int pph_error_norms_sampled(pph_ctx* ctx, const double* nodal_host, int nq, int64_t cell_begin, int64_t cell_count,
                             const double* exact_q_host, const double* grad_q_host, double* l2sq_out, double* h1sq_out);
+/* The same norms of a nodal field held in DEVICE memory (caller-owned, n local values; read on the context stream, not
+ * uploaded).  On a slab context (multi-GPU) they are collective: every rank calls, the ghost planes of a copy of the field
+ * are refreshed from their owners, each rank integrates over the cells it owns (the cell layer below its lowest owned node
+ * plane belongs to the neighbour) and the squared partials are summed over the ranks through the communication hooks.
+ * pph_error_norms_sampled_device walks the owned cells in chunks, as pph_error_norms_sampled does: a call with nodal_dev
+ * starts a sequence (the field must stay valid until its last call; on a slab its ghost planes are refreshed here, once:
+ * collective), a call with NULL continues it; every call adds the squared partials of its cells (inside the owned cells;
+ * cell_count 0 allowed) to the sequence's sums and returns them - this rank's own, or, on the call with last != 0, summed
+ * over the ranks (collective) and the sequence ends.  Ranks may make different numbers of calls in between.  The samples
+ * stay host arrays. */
+int pph_error_norms_mms_device(pph_ctx* ctx, int field, const double* nodal_dev, double k1, double k2, double beta,
+                               double mu, int nq, double* l2_out, double* h1s_out);
+int pph_error_norms_sampled_device(pph_ctx* ctx, const double* nodal_dev, int nq, int64_t cell_begin, int64_t cell_count,
+                                   const double* exact_q_host, const double* grad_q_host, int last, double* l2sq_out,
+                                   double* h1sq_out);
 
 /* Darcy velocity u = -conductivity * grad(p_h), L2-projected onto the CG-1 vector space of the mesh
  * replaces: calculate_darcy_velocity_from_pressure() (reference src/perphil/utils/postprocessing.py:34-63,
  * fd.project(-k grad p, VectorFunctionSpace(mesh, "CG", 1))).  p_host: n nodal pressures; u_host: [n][dim]
  * (node-major, like a Firedrake vector Function's dat).  Mass-matrix solves run to rtol 1e-13. */
 int pph_darcy_velocity(pph_ctx* ctx, const double* p_host, double conductivity, double* u_host);
+/* the same projection from a DEVICE pressure p_dev (n values) into a DEVICE u_dev ([n][dim], node-major); both caller-owned,
+ * the last writes to u_dev are enqueued on the context stream */
+int pph_darcy_velocity_device(pph_ctx* ctx, const double* p_dev, double conductivity, double* u_dev);
 
 /* ---- multi-GPU communication hooks -------------------------------------------------------------
  * replaces: PETSc's implicit VecScatter halo exchange and VecDot all-reduce under mpiexec (never run in

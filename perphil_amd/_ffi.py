@@ -37,6 +37,8 @@ EXPORTS = [
     "pph_rccl_available", "pph_rccl_unique_id", "pph_comm_init_rccl", "pph_comm_selftest", "pph_comm_selftest2",
     "pph_comm_stats", "pph_comm_times", "pph_error_norms_mms", "pph_quadrature_points", "pph_error_norms_sampled", "pph_bw_probe",
     "pph_darcy_velocity",
+    "pph_get_stream", "pph_copy_solution_device", "pph_set_dirichlet_device", "pph_error_norms_mms_device",
+    "pph_error_norms_sampled_device", "pph_darcy_velocity_device",
 ]
 
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64)
@@ -165,6 +167,14 @@ def _load() -> C.CDLL:
         "pph_darcy_velocity": ([p, C.c_void_p, C.c_double, C.c_void_p], C.c_int),
         "pph_quadrature_points": ([p, C.c_int, C.c_int64, C.c_int64, C.c_void_p], C.c_int),
         "pph_error_norms_sampled": ([p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, f64p, f64p], C.c_int),
+        "pph_get_stream": ([p, C.POINTER(C.c_void_p)], C.c_int),
+        "pph_copy_solution_device": ([p, C.c_void_p, C.c_int64], C.c_int),
+        "pph_set_dirichlet_device": ([p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64], C.c_int),
+        "pph_error_norms_mms_device": ([p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
+                                        f64p, f64p], C.c_int),
+        "pph_error_norms_sampled_device": ([p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+                                            f64p, f64p], C.c_int),
+        "pph_darcy_velocity_device": ([p, C.c_void_p, C.c_double, C.c_void_p], C.c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = ABI mismatch: fail loudly
@@ -182,6 +192,68 @@ class ConvergenceError(RuntimeError):
 
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+# -- device-resident results ------------------------------------------------------------------------
+# Torch tensors and this library share one HIP runtime when torch's copy of it was loaded first (_preload_hip_runtime):
+# device pointers then cross freely and results can stay in GPU memory.  With PERPHIL_HIP_RUNTIME=system, without torch,
+# or when two runtimes ended up in the process anyway, they cannot: results are copied to the host as before.
+_shared: Optional[bool] = None
+
+# solution-sized device-to-host copies made so far (solves with fetch, Context.solution, first host access of a
+# device-resident fd.Function): what a caller who keeps results on the device should see stay at zero
+fetch_stats = {"fetches": 0, "bytes": 0}
+
+
+def _count_fetch(nbytes: int) -> None:
+    fetch_stats["fetches"] += 1
+    fetch_stats["bytes"] += int(nbytes)
+
+
+def shared_runtime() -> bool:
+    """True when torch's device tensors and this library's device pointers belong to one HIP runtime."""
+    global _shared
+    if _shared is None:
+        _shared = _probe_shared_runtime()
+    return _shared
+
+
+def _probe_shared_runtime() -> bool:
+    if os.environ.get("PERPHIL_HIP_RUNTIME", "") == "system":
+        return False
+    try:
+        import torch
+    except ImportError:
+        return False
+    if not getattr(torch.version, "hip", None):
+        return False
+    try:
+        with open("/proc/self/maps") as f:
+            libs = {os.path.realpath(line.split()[-1]) for line in f if "libamdhip64.so" in line}
+    except OSError:
+        libs = set()
+    return len(libs) <= 1
+
+
+def require_shared_runtime(what: str) -> None:
+    if not shared_runtime():
+        raise RuntimeError(f"{what} needs torch and this library on one HIP runtime (torch installed, imported through "
+                           "perphil_amd's preload, PERPHIL_HIP_RUNTIME not 'system'); copy the data to the host instead")
+
+
+def _tptr(t) -> C.c_void_p:
+    return C.c_void_p(t.data_ptr())
+
+
+def tensor_to_host(t, ctx: Optional["Context"] = None) -> np.ndarray:
+    """float64 device tensor -> NumPy array (the context's pinned result pool for large ones), on torch's current stream."""
+    import torch
+
+    n = t.numel()
+    arr = ctx._result_array(n) if ctx is not None else np.empty(n, dtype=np.float64)
+    torch.from_numpy(arr).copy_(t.reshape(-1))
+    _count_fetch(8 * n)
+    return arr
 
 
 class Context:
@@ -244,6 +316,9 @@ class Context:
         self._check(lib.pph_mesh_sizes(self._h, C.byref(n), C.byref(nc), C.byref(m), C.byref(nnz)))
         self.n, self.ncell, self.m, self.nnzb, self.dim = n.value, nc.value, m.value, nnz.value, dim
         self._bc_state = {}
+        # cells of the device norms (pph_error_norms_*_device): a slab leaves the layer above its lower ghost plane to the
+        # neighbour that owns the plane
+        self._slab_cells = (self.ncell // z_count if ghost_lo and dim == 3 else 0, self.ncell)
 
     def dofmap(self) -> np.ndarray:
         out = np.empty((self.ncell, self.m), dtype=np.int32)
@@ -264,12 +339,23 @@ class Context:
         self._check(lib.pph_set_dirichlet(self._h, int(field), _ptr(nodes), _ptr(vals), nodes.size))
         self._bc_state[int(field)] = (nodes.copy(), vals.copy())
 
-    def same_dirichlet(self, field: int, nodes: np.ndarray, vals: np.ndarray) -> bool:
+    def same_dirichlet(self, field: int, nodes, vals) -> bool:
         """True when exactly this set (nodes and values) is what the device holds for `field` (callers skip the
-        upload then: pph_set_dirichlet drops the assembled system and makes the multigrid levels re-derive their masks)."""
+        upload then: pph_set_dirichlet drops the assembled system and makes the multigrid levels re-derive their masks).
+        Device tensors are compared on the device with the set a tensor call left; a host set and a device set are
+        never taken for the same one (the set is applied again)."""
         old = self._bc_state.get(int(field))
-        return (old is not None and np.array_equal(old[0], np.asarray(nodes, dtype=np.int64))
-                and np.array_equal(old[1], np.asarray(vals, dtype=np.float64)))
+        if old is None:
+            return False
+        if isinstance(old[1], np.ndarray) != isinstance(vals, np.ndarray):
+            return False
+        if isinstance(vals, np.ndarray):
+            return (np.array_equal(old[0], np.asarray(nodes, dtype=np.int64))
+                    and np.array_equal(old[1], np.asarray(vals, dtype=np.float64)))
+        import torch
+
+        return (old[0].shape == nodes.shape and old[1].shape == vals.shape and torch.equal(old[0], nodes)
+                and torch.equal(old[1], vals))
 
     def assemble(self, k1: float, k2: float, beta: float, mu: float, monolithic: bool = True) -> None:
         self._check(lib.pph_assemble_dpp(self._h, float(k1), float(k2), float(beta), float(mu), int(monolithic)))
@@ -319,6 +405,7 @@ class Context:
         hist = np.zeros(max(hist_cap, 1), dtype=np.float64)
         x = self._result_array(2 * self.n) if fetch else None
         if fetch:
+            _count_fetch(8 * x.size)
             st = lib.pph_solve(self._h, C.byref(cfg), _ptr(x), C.byref(info), _ptr(hist), int(hist_cap))
         else:
             st = lib.pph_solve_device(self._h, C.byref(cfg), C.byref(info), _ptr(hist), int(hist_cap))
@@ -329,7 +416,120 @@ class Context:
     def solution(self) -> np.ndarray:
         x = self._result_array(2 * self.n)
         self._check(lib.pph_get_solution(self._h, _ptr(x)))
+        _count_fetch(8 * x.size)
         return x
+
+    # -- device-resident results (torch tensors; shared runtime only) -------------------------
+    def torch_device(self):
+        import torch
+
+        return torch.device("cuda", self.device)
+
+    def torch_stream(self):
+        """The context's stream as a ``torch.cuda.ExternalStream``."""
+        st = self.__dict__.get("_tstream")
+        if st is None or self.__dict__.get("_tstream_h") != self._h.value:
+            import torch
+
+            require_shared_runtime("a device-resident result")
+            ptr = C.c_void_p()
+            self._check(lib.pph_get_stream(self._h, C.byref(ptr)))
+            st = torch.cuda.ExternalStream(ptr.value, device=self.torch_device())
+            self._tstream, self._tstream_h = st, self._h.value
+        return st
+
+    def wait_for_torch(self) -> None:
+        """Torch -> library: the context stream waits for the work torch has enqueued so far (no host wait)."""
+        import torch
+
+        self.torch_stream().wait_stream(torch.cuda.current_stream(self.torch_device()))
+
+    def torch_waits(self) -> None:
+        """Library -> torch: torch's current stream waits for the work enqueued on the context stream so far."""
+        import torch
+
+        torch.cuda.current_stream(self.torch_device()).wait_stream(self.torch_stream())
+
+    # Blocks of torch's allocator and the context stream: no record_stream on the context stream - the allocator would
+    # record an event on that stream when the tensor dies, which may be after close() destroyed the stream.  Instead every
+    # entry point that writes a tensor is followed at once by torch_waits() (torch's current stream, the block's own, waits
+    # for the write: a block freed later is reused after it), and every entry point that reads one returns only after the
+    # context stream has finished reading (it synchronises).
+    def _device_out(self, n: int):
+        """A fresh float64 tensor of torch's caching allocator for the context stream to write into (call torch_waits()
+        right after the write)."""
+        import torch
+
+        t = torch.empty(n, dtype=torch.float64, device=self.torch_device())
+        self.wait_for_torch()                  # (the block may still be read by torch work enqueued earlier)
+        return t
+
+    def _device_in(self, t, n: int, name: str):
+        """Checks a caller's device tensor and orders the context stream after torch's work on it."""
+        import torch
+
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.is_cuda and t.shape == (n,)
+                and t.is_contiguous() and t.device.index == self.device):
+            raise ValueError(f"{name} must be a contiguous float64 tensor of {n} values on cuda:{self.device}")
+        self.wait_for_torch()
+        return t
+
+    def solution_tensor(self):
+        """The current solution copied (on the device) into a new torch tensor; torch's current stream is ordered after it."""
+        t = self._device_out(2 * self.n)
+        self._check(lib.pph_copy_solution_device(self._h, _tptr(t), t.numel()))
+        self.torch_waits()
+        return t
+
+    def set_dirichlet_device(self, field: int, nodes, vals) -> None:
+        """pph_set_dirichlet from device tensors (int64 nodes, float64 values)."""
+        import torch
+
+        if nodes.dtype != torch.int64 or not nodes.is_cuda or nodes.dim() != 1 or not nodes.is_contiguous():
+            raise ValueError("nodes must be a contiguous int64 tensor on the device")
+        vals = self._device_in(vals, nodes.numel(), "vals")
+        self._check(lib.pph_set_dirichlet_device(self._h, int(field), _tptr(nodes), _tptr(vals), nodes.numel()))
+        self._bc_state[int(field)] = (nodes.clone(), vals.clone())
+
+    def error_norms_mms_device(self, field: int, nodal, k1: float, k2: float, beta: float, mu: float, nq: int = 6):
+        """error_norms_mms of a device tensor (collective on a slab: owned cells, summed over the ranks)."""
+        nodal = self._device_in(nodal, self.n, "nodal field")
+        l2, h1 = C.c_double(), C.c_double()
+        self._check(lib.pph_error_norms_mms_device(self._h, int(field), _tptr(nodal), float(k1), float(k2), float(beta),
+                                                   float(mu), int(nq), C.byref(l2), C.byref(h1)))
+        return l2.value, h1.value
+
+    def owned_cells(self) -> tuple:
+        """[begin, end) of the cells this context integrates over in the device norms (all of them on a single context)."""
+        s = self.__dict__.get("_slab_cells")
+        return s if s is not None else (0, self.ncell)
+
+    def error_norms_sampled_device(self, nodal, exact, grad=None, nq: int = 6, chunk_cells: int = 1 << 16):
+        """error_norms_sampled of a device tensor, over this context's owned cells in chunks (collective on a slab: the
+        field's ghost planes are refreshed by the first call, the sums are reduced over the ranks by the last)."""
+        nodal = self._device_in(nodal, self.n, "nodal field")
+        c0, c1 = self.owned_cells()
+        if exact is None:
+            chunk_cells = max(c1 - c0, 1)
+        starts = list(range(c0, c1, chunk_cells)) or [c1]
+        a, b = C.c_double(), C.c_double()
+        for k, b0 in enumerate(starts):
+            cnt = min(chunk_cells, c1 - b0)
+            se = sg = None
+            if exact is not None and cnt > 0:
+                se, sg = self._samples(exact, grad, nq, b0, cnt)
+            self._check(lib.pph_error_norms_sampled_device(self._h, _tptr(nodal) if k == 0 else None, int(nq), int(b0),
+                                                           int(cnt), _ptr(se), _ptr(sg), int(k == len(starts) - 1),
+                                                           C.byref(a), C.byref(b)))
+        return float(np.sqrt(a.value)), float(np.sqrt(b.value))
+
+    def darcy_velocity_device(self, nodal, conductivity: float):
+        """darcy_velocity of a device tensor; returns a device tensor [n * dim] (node-major)."""
+        nodal = self._device_in(nodal, self.n, "pressure")
+        out = self._device_out(self.n * self.dim)
+        self._check(lib.pph_darcy_velocity_device(self._h, _tptr(nodal), float(conductivity), _tptr(out)))
+        self.torch_waits()
+        return out
 
     # -- export -------------------------------------------------------------------------------
     def csr(self, which: int):
@@ -393,19 +593,7 @@ class Context:
             cnt = min(chunk_cells, self.ncell - c0)
             se = sg = None
             if exact is not None:
-                X = self.quadrature_points(nq, c0, cnt)
-                se = np.ascontiguousarray(exact(X), dtype=np.float64).reshape(-1)
-                if grad is not None:
-                    sg = np.ascontiguousarray(grad(X), dtype=np.float64).reshape(-1, self.dim)
-                else:
-                    h = 1e-6
-                    sg = np.empty_like(X)
-                    for d in range(self.dim):
-                        E = np.zeros(self.dim)
-                        E[d] = h
-                        sg[:, d] = (np.asarray(exact(X + E), dtype=np.float64).reshape(-1)
-                                    - np.asarray(exact(X - E), dtype=np.float64).reshape(-1)) / (2 * h)
-                    sg = np.ascontiguousarray(sg)
+                se, sg = self._samples(exact, grad, nq, c0, cnt)
             # the nodal field travels with the first chunk only (NULL afterwards = the field of the previous call)
             self._check(lib.pph_error_norms_sampled(self._h, _ptr(nodal) if first else None, int(nq), int(c0), int(cnt),
                                                     _ptr(se), _ptr(sg), C.byref(a), C.byref(b)))
@@ -413,6 +601,23 @@ class Context:
             l2 += a.value
             h1 += b.value
         return float(np.sqrt(l2)), float(np.sqrt(h1))
+
+    def _samples(self, exact, grad, nq: int, c0: int, cnt: int):
+        """Exact field and gradient at the quadrature points of cells [c0, c0 + cnt) (host arrays)."""
+        X = self.quadrature_points(nq, c0, cnt)
+        se = np.ascontiguousarray(exact(X), dtype=np.float64).reshape(-1)
+        if grad is not None:
+            sg = np.ascontiguousarray(grad(X), dtype=np.float64).reshape(-1, self.dim)
+        else:
+            h = 1e-6
+            sg = np.empty_like(X)
+            for d in range(self.dim):
+                E = np.zeros(self.dim)
+                E[d] = h
+                sg[:, d] = (np.asarray(exact(X + E), dtype=np.float64).reshape(-1)
+                            - np.asarray(exact(X - E), dtype=np.float64).reshape(-1)) / (2 * h)
+            sg = np.ascontiguousarray(sg)
+        return se, sg
 
     def darcy_velocity(self, nodal: np.ndarray, conductivity: float) -> np.ndarray:
         """L2 projection of -conductivity * grad(p_h) onto CG-1 vectors; returns [n, dim]."""

@@ -68,6 +68,15 @@ __global__ __launch_bounds__(256) void k_dirichlet_set(uint8_t* __restrict__ mas
   }
 }
 
+// number of node ids outside [0, n) -> *bad (the device lists are checked before anything is scattered through them)
+__global__ __launch_bounds__(256) void k_count_out_of_range(const int64_t* __restrict__ nodes, int64_t count, int64_t n,
+                                                            unsigned long long* __restrict__ bad) {
+  unsigned long long c = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x)
+    c += (nodes[i] < 0 || nodes[i] >= n) ? 1ull : 0ull;
+  if (c) atomicAdd(bad, c);
+}
+
 extern "C" {
 
 const char* pph_last_error(const pph_ctx* ctx) { return ctx ? ctx->err.c_str() : g_last_error.c_str(); }
@@ -168,6 +177,7 @@ int pph_ctx_destroy(pph_ctx* ctx) {
   ctx->rownear.release();
   ctx->sell_tmp.release();
   ctx->post_u.release();
+  ctx->bc_bad.release();
   ctx->dinv0[0].release(); ctx->dinv0[1].release(); ctx->lam0.release();
   comm_release(ctx);
   for (auto& w : ctx->work) w.release();
@@ -294,6 +304,24 @@ int pph_get_coords(pph_ctx* ctx, double* coords_host) {
 }
 
 // ---- Dirichlet data -----------------------------------------------------------------------------
+// device half shared by pph_set_dirichlet and pph_set_dirichlet_device: (node, value) lists already on the device and in
+// range; mask and boundary-value vector of `field` are rebuilt from them on the context stream
+static int dirichlet_apply(pph_ctx* ctx, int field, const int64_t* dn, const double* dv, int64_t count) {
+  const int64_t n = ctx->n;
+  release_system(ctx);  // any assembled system is stale now
+  PPH_HIP(ctx, hipMemsetAsync(ctx->g[field].p, 0, sizeof(double) * (size_t)n, ctx->stream));
+  const int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+  hipLaunchKernelGGL(k_dirichlet_clear, dim3(grid < 1 ? 1 : grid), dim3(256), 0, ctx->stream, ctx->bcmask[field].p, n);
+  if (count > 0) {
+    const int g2 = (int)((count + 255) / 256 < 4096 ? (count + 255) / 256 : 4096);
+    hipLaunchKernelGGL(k_dirichlet_set, dim3(g2), dim3(256), 0, ctx->stream, ctx->bcmask[field].p, ctx->g[field].p, dn,
+                       dv, count);
+  }
+  ctx->bc_dirty = true;
+  ctx->bc_epoch++;
+  return PPH_OK;
+}
+
 int pph_set_dirichlet(pph_ctx* ctx, int field, const int64_t* nodes, const double* vals, int64_t count) {
   if (!ctx) return PPH_ERR_INVALID;
   PPH_HIP(ctx, hipSetDevice(ctx->device));
@@ -304,7 +332,6 @@ int pph_set_dirichlet(pph_ctx* ctx, int field, const int64_t* nodes, const doubl
   for (int64_t i = 0; i < count; ++i)
     PPH_REQUIRE(ctx, nodes[i] >= 0 && nodes[i] < n, "Dirichlet node %lld outside [0,%lld)", (long long)nodes[i],
                 (long long)n);
-  release_system(ctx);  // any assembled system is stale now
   // only the (node, value) list travels to the device; mask and boundary-value vector are rebuilt there (a node listed
   // more than once must carry the same value in all its entries)
   DevBuf<int64_t> dn;
@@ -315,18 +342,40 @@ int pph_set_dirichlet(pph_ctx* ctx, int field, const int64_t* nodes, const doubl
     PPH_HIP(ctx, hipMemcpyAsync(dn.p, nodes, sizeof(int64_t) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
     PPH_HIP(ctx, hipMemcpyAsync(dv.p, vals, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
   }
-  PPH_HIP(ctx, hipMemsetAsync(ctx->g[field].p, 0, sizeof(double) * (size_t)n, ctx->stream));
-  const int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-  hipLaunchKernelGGL(k_dirichlet_clear, dim3(grid < 1 ? 1 : grid), dim3(256), 0, ctx->stream, ctx->bcmask[field].p, n);
-  if (count > 0) {
-    const int g2 = (int)((count + 255) / 256 < 4096 ? (count + 255) / 256 : 4096);
-    hipLaunchKernelGGL(k_dirichlet_set, dim3(g2), dim3(256), 0, ctx->stream, ctx->bcmask[field].p, ctx->g[field].p, dn.p,
-                       dv.p, count);
-  }
-  ctx->bc_dirty = true;
-  ctx->bc_epoch++;
+  PPH_TRY(dirichlet_apply(ctx, field, dn.p, dv.p, count));
   PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the caller's arrays and the staging buffers are free again)
   PPH_HIP(ctx, hipGetLastError());
+  return PPH_OK;
+}
+
+int pph_set_dirichlet_device(pph_ctx* ctx, int field, const int64_t* nodes, const double* vals, int64_t count) {
+  if (!ctx) return PPH_ERR_INVALID;
+  PPH_HIP(ctx, hipSetDevice(ctx->device));
+  PPH_REQUIRE(ctx, ctx->mesh_ok, "pph_set_dirichlet_device before pph_mesh_build");
+  PPH_REQUIRE(ctx, field == 0 || field == 1, "field must be 0 or 1, got %d", field);
+  PPH_REQUIRE(ctx, count >= 0 && (count == 0 || (nodes && vals)), "NULL nodes/vals with count %lld", (long long)count);
+  if (count > 0) {
+    // the same range check as the host entry point, on the device: one counter travels back
+    DevBuf<unsigned long long>& bad = ctx->bc_bad;   // (one word kept by the context: no allocation per call)
+    PPH_TRY(bad.alloc(ctx, 1));
+    PPH_HIP(ctx, hipMemsetAsync(bad.p, 0, sizeof(unsigned long long), ctx->stream));
+    const int g = (int)((count + 255) / 256 < 1024 ? (count + 255) / 256 : 1024);
+    hipLaunchKernelGGL(k_count_out_of_range, dim3(g), dim3(256), 0, ctx->stream, nodes, count, ctx->n, bad.p);
+    unsigned long long nbad = 0;
+    PPH_HIP(ctx, hipMemcpyAsync(&nbad, bad.p, sizeof(nbad), hipMemcpyDeviceToHost, ctx->stream));
+    PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PPH_REQUIRE(ctx, nbad == 0, "%llu Dirichlet nodes outside [0,%lld)", nbad, (long long)ctx->n);
+  }
+  PPH_TRY(dirichlet_apply(ctx, field, nodes, vals, count));
+  PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the caller's device arrays are free again)
+  PPH_HIP(ctx, hipGetLastError());
+  return PPH_OK;
+}
+
+int pph_get_stream(pph_ctx* ctx, void** stream) {
+  if (!ctx) return PPH_ERR_INVALID;
+  PPH_REQUIRE(ctx, stream != nullptr, "stream is NULL");
+  *stream = (void*)ctx->stream;
   return PPH_OK;
 }
 

@@ -462,6 +462,9 @@ struct pph_ctx {
   DevBuf<double> sell_tmp;              // SELL copy of the matrix last selected by pph_spmv / pph_spmv_bench
   DevBuf<double> post_u;                // nodal field of the last pph_error_norms_sampled call (chunked callers upload it once)
   bool post_u_valid = false;
+  const double* post_dev_u = nullptr;   // field of the running pph_error_norms_sampled_device sequence (caller's or post_u)
+  double post_dev_sum[2] = {0, 0};      // its running squared partials
+  DevBuf<unsigned long long> bc_bad;    // pph_set_dirichlet_device: count of out-of-range node ids
 };
 
 // lanes per row of the CSR-vector SpMV for a matrix with the given mean row length

@@ -342,6 +342,70 @@ static void gauss_legendre(int n, double* x, double* w) {
   }
 }
 
+// cells [*c0, *c1) this context integrates over: all of them on a single context; on a slab the cell layer between a
+// ghost plane below and the lowest owned plane is left to the neighbour that owns that plane (it holds the same layer
+// as its top one), so every cell of the global mesh is counted on exactly one rank
+static void owned_cells(const pph_ctx* ctx, int64_t* c0, int64_t* c1) {
+  const MeshData& m = ctx->mesh;
+  const int64_t layers = (m.dim == 3 && m.nzl > 0) ? m.nzl : 1;
+  *c0 = m.glo ? m.ncell / layers : 0;
+  *c1 = m.ncell;
+}
+
+// the nodal field the norm kernels read: the caller's device array itself on a single context; on a slab a copy whose
+// ghost planes are refreshed from their owners (collective: every rank calls)
+static int norms_field(pph_ctx* ctx, const double* nodal_dev, const double** u) {
+  const MeshData& m = ctx->mesh;
+  *u = nodal_dev;
+  if (ctx->world <= 1 || (!m.glo && !m.ghi)) return PPH_OK;
+  ctx->post_u_valid = false;
+  PPH_TRY(ctx->post_u.alloc(ctx, (size_t)m.n));
+  la_copy(ctx, ctx->post_u.p, nodal_dev, m.n);
+  PPH_TRY(la_halo(ctx, m, ctx->post_u.p));
+  *u = ctx->post_u.p;
+  return PPH_OK;
+}
+
+// squared L2 / H1-seminorm errors of the device field u against the manufactured pressure `field`, over cells [c0, c1)
+static int norms_mms(pph_ctx* ctx, int field, const double* u, int64_t c0, int64_t c1, double k1, double k2, double beta,
+                     double mu, int nq, double r[2]) {
+  const MeshData& m = ctx->mesh;
+  r[0] = r[1] = 0.0;
+  const int64_t count = c1 - c0;
+  if (count <= 0) return PPH_OK;
+  DevBuf<double> part;
+  PPH_TRY(part.alloc(ctx, 2 * 2048 + 2));
+  GaussRule g;
+  g.nq = nq;
+  gauss_legendre(nq, g.x, g.w);
+  MmsPar p;
+  p.mu = mu;
+  p.mu_over_pi = mu / 3.14159265358979323846;
+  p.eta = std::sqrt(beta * (k1 + k2) / (k1 * k2));
+  p.coef_e = (field == 0) ? -mu / (beta * k1) : mu / (beta * k2);
+  int64_t nb = ceil_div64(count, 256);
+  const int grid = (int)(nb < 2048 ? nb : 2048);
+  const int32_t* cells = m.cells.p + c0 * m.m;   // (the closed-form source reads no per-cell samples: a cell range is an offset)
+  if (m.kind == PPH_CELL_QUAD)
+    hipLaunchKernelGGL(k_error_norms<2>, dim3(grid), dim3(256), 0, ctx->stream, cells, m.cx.p, m.cy.p, m.cz.p, u, g,
+                       p, count, part.p);
+  else if (m.kind == PPH_CELL_TRI)
+    hipLaunchKernelGGL(k_error_norms_simplex<2>, dim3(grid), dim3(256), 0, ctx->stream, cells, m.cx.p, m.cy.p, m.cz.p,
+                       u, g, p, count, part.p);
+  else if (m.kind == PPH_CELL_TET)
+    hipLaunchKernelGGL(k_error_norms_simplex<3>, dim3(grid), dim3(256), 0, ctx->stream, cells, m.cx.p, m.cy.p, m.cz.p,
+                       u, g, p, count, part.p);
+  else
+    hipLaunchKernelGGL(k_error_norms<3>, dim3(grid), dim3(256), 0, ctx->stream, cells, m.cx.p, m.cy.p, m.cz.p, u, g,
+                       p, count, part.p);
+  hipLaunchKernelGGL(k_sum_partials, dim3(2), dim3(256), 0, ctx->stream, part.p, grid, part.p + 4096);
+  PPH_HIP(ctx, hipMemcpyAsync(r, part.p + 4096, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  PPH_HIP(ctx, hipGetLastError());
+  part.release();
+  return PPH_OK;
+}
+
 extern "C" int pph_error_norms_mms(pph_ctx* ctx, int field, const double* nodal_host, double k1, double k2,
                                    double beta, double mu, int nq, double* l2_out, double* h1s_out) {
   if (!ctx) return PPH_ERR_INVALID;
@@ -352,41 +416,34 @@ extern "C" int pph_error_norms_mms(pph_ctx* ctx, int field, const double* nodal_
   PPH_REQUIRE(ctx, nq >= 1 && nq <= 8 && nodal_host && l2_out && h1s_out, "bad arguments");
   PPH_REQUIRE(ctx, k1 > 0 && k2 > 0 && mu > 0 && beta > 0, "need positive parameters");
   PPH_HIP(ctx, hipSetDevice(ctx->device));
-  DevBuf<double> u, part;
+  DevBuf<double> u;
   PPH_TRY(u.alloc(ctx, (size_t)m.n));
-  PPH_TRY(part.alloc(ctx, 2 * 2048 + 2));
   PPH_HIP(ctx, hipMemcpyAsync(u.p, nodal_host, sizeof(double) * (size_t)m.n, hipMemcpyHostToDevice, ctx->stream));
-  GaussRule g;
-  g.nq = nq;
-  gauss_legendre(nq, g.x, g.w);
-  MmsPar p;
-  p.mu = mu;
-  p.mu_over_pi = mu / 3.14159265358979323846;
-  p.eta = std::sqrt(beta * (k1 + k2) / (k1 * k2));
-  p.coef_e = (field == 0) ? -mu / (beta * k1) : mu / (beta * k2);
-  int64_t nb = ceil_div64(m.ncell, 256);
-  const int grid = (int)(nb < 2048 ? nb : 2048);
-  if (m.kind == PPH_CELL_QUAD)
-    hipLaunchKernelGGL(k_error_norms<2>, dim3(grid), dim3(256), 0, ctx->stream, m.cells.p, m.cx.p, m.cy.p, m.cz.p, u.p, g,
-                       p, m.ncell, part.p);
-  else if (m.kind == PPH_CELL_TRI)
-    hipLaunchKernelGGL(k_error_norms_simplex<2>, dim3(grid), dim3(256), 0, ctx->stream, m.cells.p, m.cx.p, m.cy.p, m.cz.p,
-                       u.p, g, p, m.ncell, part.p);
-  else if (m.kind == PPH_CELL_TET)
-    hipLaunchKernelGGL(k_error_norms_simplex<3>, dim3(grid), dim3(256), 0, ctx->stream, m.cells.p, m.cx.p, m.cy.p, m.cz.p,
-                       u.p, g, p, m.ncell, part.p);
-  else
-    hipLaunchKernelGGL(k_error_norms<3>, dim3(grid), dim3(256), 0, ctx->stream, m.cells.p, m.cx.p, m.cy.p, m.cz.p, u.p, g,
-                       p, m.ncell, part.p);
-  hipLaunchKernelGGL(k_sum_partials, dim3(2), dim3(256), 0, ctx->stream, part.p, grid, part.p + 4096);
   double r[2];
-  PPH_HIP(ctx, hipMemcpyAsync(r, part.p + 4096, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
-  PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  PPH_HIP(ctx, hipGetLastError());
+  PPH_TRY(norms_mms(ctx, field, u.p, 0, m.ncell, k1, k2, beta, mu, nq, r));
   *l2_out = std::sqrt(r[0]);
   *h1s_out = std::sqrt(r[1]);
   u.release();
-  part.release();
+  return PPH_OK;
+}
+
+extern "C" int pph_error_norms_mms_device(pph_ctx* ctx, int field, const double* nodal_dev, double k1, double k2,
+                                          double beta, double mu, int nq, double* l2_out, double* h1s_out) {
+  if (!ctx) return PPH_ERR_INVALID;
+  PPH_REQUIRE(ctx, ctx->mesh_ok, "pph_error_norms_mms_device before pph_mesh_build");
+  PPH_REQUIRE(ctx, field == 0 || field == 1, "field must be 0 or 1");
+  PPH_REQUIRE(ctx, nq >= 1 && nq <= 8 && nodal_dev && l2_out && h1s_out, "bad arguments");
+  PPH_REQUIRE(ctx, k1 > 0 && k2 > 0 && mu > 0 && beta > 0, "need positive parameters");
+  PPH_HIP(ctx, hipSetDevice(ctx->device));
+  const double* u = nullptr;
+  PPH_TRY(norms_field(ctx, nodal_dev, &u));
+  int64_t c0, c1;
+  owned_cells(ctx, &c0, &c1);
+  double r[2];
+  PPH_TRY(norms_mms(ctx, field, u, c0, c1, k1, k2, beta, mu, nq, r));
+  PPH_TRY(comm_allreduce_host(ctx, r, 2));   // (no-op on a single context)
+  *l2_out = std::sqrt(r[0]);
+  *h1s_out = std::sqrt(r[1]);
   return PPH_OK;
 }
 
@@ -427,6 +484,42 @@ extern "C" int pph_quadrature_points(pph_ctx* ctx, int nq, int64_t cell_begin, i
   return PPH_OK;
 }
 
+// squared partial norms of the device field u over cells [c0, c0 + count) against device samples se / sg (may be null)
+static int norms_sampled(pph_ctx* ctx, const double* u, int nq, int64_t c0, int64_t count, const double* se,
+                         const double* sg, double r[2]) {
+  const MeshData& m = ctx->mesh;
+  DevBuf<double> part;
+  PPH_TRY(part.alloc(ctx, 2 * 2048 + 2));
+  GaussRule g;
+  g.nq = nq;
+  gauss_legendre(nq, g.x, g.w);
+  ErrSamples es{se, sg, nullptr, c0, c0 + count};
+  const int64_t nb = ceil_div64(count, 256);
+  const int grid = (int)(nb < 2048 ? nb : 2048);
+  err_launch<1>(ctx, m, u, g, part.p, es, grid);
+  hipLaunchKernelGGL(k_sum_partials, dim3(2), dim3(256), 0, ctx->stream, part.p, grid, part.p + 4096);
+  PPH_HIP(ctx, hipMemcpyAsync(r, part.p + 4096, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  PPH_HIP(ctx, hipGetLastError());
+  part.release();
+  return PPH_OK;
+}
+
+// uploads the caller's host samples of cells [c0, c0 + count) (null stays null)
+static int upload_samples(pph_ctx* ctx, int64_t count, int64_t npts, const double* exact_q_host, const double* grad_q_host,
+                          DevBuf<double>& se, DevBuf<double>& sg) {
+  const MeshData& m = ctx->mesh;
+  if (exact_q_host) {
+    PPH_TRY(se.alloc(ctx, (size_t)(count * npts)));
+    PPH_HIP(ctx, hipMemcpyAsync(se.p, exact_q_host, sizeof(double) * (size_t)(count * npts), hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (grad_q_host) {
+    PPH_TRY(sg.alloc(ctx, (size_t)(count * npts * m.dim)));
+    PPH_HIP(ctx, hipMemcpyAsync(sg.p, grad_q_host, sizeof(double) * (size_t)(count * npts * m.dim), hipMemcpyHostToDevice, ctx->stream));
+  }
+  return PPH_OK;
+}
+
 extern "C" int pph_error_norms_sampled(pph_ctx* ctx, const double* nodal_host, int nq, int64_t cell_begin, int64_t cell_count,
                                        const double* exact_q_host, const double* grad_q_host, double* l2sq_out, double* h1sq_out) {
   if (!ctx) return PPH_ERR_INVALID;
@@ -441,38 +534,61 @@ extern "C" int pph_error_norms_sampled(pph_ctx* ctx, const double* nodal_host, i
               "pph_error_norms_sampled: no nodal field (NULL means: the one of the previous call)");
   PPH_HIP(ctx, hipSetDevice(ctx->device));
   const int64_t npts = (m.dim == 2) ? nq * nq : nq * nq * nq;
-  DevBuf<double> part, se, sg;
+  DevBuf<double> se, sg;
   DevBuf<double>& u = ctx->post_u;
-  PPH_TRY(part.alloc(ctx, 2 * 2048 + 2));
   if (nodal_host) {
     ctx->post_u_valid = false;
     PPH_TRY(u.alloc(ctx, (size_t)m.n));
     PPH_HIP(ctx, hipMemcpyAsync(u.p, nodal_host, sizeof(double) * (size_t)m.n, hipMemcpyHostToDevice, ctx->stream));
     ctx->post_u_valid = true;
   }
-  if (exact_q_host) {
-    PPH_TRY(se.alloc(ctx, (size_t)(cell_count * npts)));
-    PPH_HIP(ctx, hipMemcpyAsync(se.p, exact_q_host, sizeof(double) * (size_t)(cell_count * npts), hipMemcpyHostToDevice, ctx->stream));
-  }
-  if (grad_q_host) {
-    PPH_TRY(sg.alloc(ctx, (size_t)(cell_count * npts * m.dim)));
-    PPH_HIP(ctx, hipMemcpyAsync(sg.p, grad_q_host, sizeof(double) * (size_t)(cell_count * npts * m.dim), hipMemcpyHostToDevice, ctx->stream));
-  }
-  GaussRule g;
-  g.nq = nq;
-  gauss_legendre(nq, g.x, g.w);
-  ErrSamples es{exact_q_host ? se.p : nullptr, grad_q_host ? sg.p : nullptr, nullptr, cell_begin, cell_begin + cell_count};
-  const int64_t nb = ceil_div64(cell_count, 256);
-  const int grid = (int)(nb < 2048 ? nb : 2048);
-  err_launch<1>(ctx, m, u.p, g, part.p, es, grid);
-  hipLaunchKernelGGL(k_sum_partials, dim3(2), dim3(256), 0, ctx->stream, part.p, grid, part.p + 4096);
+  PPH_TRY(upload_samples(ctx, cell_count, npts, exact_q_host, grad_q_host, se, sg));
   double r[2];
-  PPH_HIP(ctx, hipMemcpyAsync(r, part.p + 4096, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
-  PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  PPH_HIP(ctx, hipGetLastError());
+  PPH_TRY(norms_sampled(ctx, u.p, nq, cell_begin, cell_count, exact_q_host ? se.p : nullptr, grad_q_host ? sg.p : nullptr, r));
   *l2sq_out = r[0];
   *h1sq_out = r[1];
-  part.release(); se.release(); sg.release();
+  se.release(); sg.release();
+  return PPH_OK;
+}
+
+extern "C" int pph_error_norms_sampled_device(pph_ctx* ctx, const double* nodal_dev, int nq, int64_t cell_begin,
+                                              int64_t cell_count, const double* exact_q_host, const double* grad_q_host,
+                                              int last, double* l2sq_out, double* h1sq_out) {
+  if (!ctx) return PPH_ERR_INVALID;
+  PPH_REQUIRE(ctx, ctx->mesh_ok, "pph_error_norms_sampled_device before pph_mesh_build");
+  const MeshData& m = ctx->mesh;
+  PPH_REQUIRE(ctx, nq >= 1 && nq <= 8 && l2sq_out && h1sq_out, "bad arguments");
+  PPH_REQUIRE(ctx, nodal_dev || ctx->post_dev_u, "pph_error_norms_sampled_device: no nodal field (NULL continues a sequence "
+              "that a call with the field started)");
+  int64_t c0, c1;
+  owned_cells(ctx, &c0, &c1);
+  PPH_REQUIRE(ctx, cell_count >= 0 && cell_begin >= c0 && cell_begin + cell_count <= c1,
+              "cell range [%lld, %lld) outside the owned cells [%lld, %lld)", (long long)cell_begin,
+              (long long)(cell_begin + cell_count), (long long)c0, (long long)c1);
+  PPH_HIP(ctx, hipSetDevice(ctx->device));
+  const int64_t npts = (m.dim == 2) ? nq * nq : nq * nq * nq;
+  if (nodal_dev) {   // a new sequence: the field (ghost planes refreshed once on a slab), sums from zero
+    ctx->post_dev_u = nullptr;
+    PPH_TRY(norms_field(ctx, nodal_dev, &ctx->post_dev_u));
+    ctx->post_dev_sum[0] = ctx->post_dev_sum[1] = 0.0;
+  }
+  if (cell_count > 0) {
+    DevBuf<double> se, sg;
+    double r[2];
+    PPH_TRY(upload_samples(ctx, cell_count, npts, exact_q_host, grad_q_host, se, sg));
+    PPH_TRY(norms_sampled(ctx, ctx->post_dev_u, nq, cell_begin, cell_count, exact_q_host ? se.p : nullptr,
+                          grad_q_host ? sg.p : nullptr, r));
+    se.release(); sg.release();
+    ctx->post_dev_sum[0] += r[0];
+    ctx->post_dev_sum[1] += r[1];
+  }
+  double r[2] = {ctx->post_dev_sum[0], ctx->post_dev_sum[1]};
+  if (last) {
+    ctx->post_dev_u = nullptr;
+    PPH_TRY(comm_allreduce_host(ctx, r, 2));   // (once per sequence; no-op on a single context)
+  }
+  *l2sq_out = r[0];
+  *h1sq_out = r[1];
   return PPH_OK;
 }
 
@@ -651,11 +767,15 @@ __global__ __launch_bounds__(256) void k_darcy_rhs_simplex(const int32_t* __rest
   }
 }
 
-extern "C" int pph_darcy_velocity(pph_ctx* ctx, const double* p_host, double conductivity, double* u_host) {
-  if (!ctx) return PPH_ERR_INVALID;
-  PPH_REQUIRE(ctx, ctx->mesh_ok && p_host && u_host, "pph_darcy_velocity: no mesh or NULL buffer");
-  PPH_REQUIRE(ctx, ctx->world == 1, "Darcy velocity projection is implemented for single-context meshes");
-  PPH_HIP(ctx, hipSetDevice(ctx->device));
+// component d of the node-major vector field u[n][dim] <- c[n]
+__global__ __launch_bounds__(256) void k_interleave(double* __restrict__ u, const double* __restrict__ c, int d, int dim,
+                                                    int64_t n) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    u[i * dim + d] = c[i];
+}
+
+// the projection of the device pressure p into u_host (host, node-major) or u_dev (device, node-major): one of the two
+static int darcy(pph_ctx* ctx, const double* p, double conductivity, double* u_host, double* u_dev) {
   MeshData& m = ctx->mesh;
   if (!m.km_valid) {
     PPH_TRY(pph_launch_assemble_KM(ctx, m));
@@ -663,42 +783,68 @@ extern "C" int pph_darcy_velocity(pph_ctx* ctx, const double* p_host, double con
   }
   const int64_t n = m.n;
   const int dim = m.dim;
-  DevBuf<double> p, b, u, dinv, w1, w2, w3, w4;
-  PPH_TRY(p.alloc(ctx, (size_t)n));
+  DevBuf<double> b, u, dinv, w1, w2, w3, w4;
   PPH_TRY(b.alloc(ctx, (size_t)n * dim));
   PPH_TRY(u.alloc(ctx, (size_t)n));
   PPH_TRY(dinv.alloc(ctx, (size_t)n));
   PPH_TRY(w1.alloc(ctx, (size_t)n)); PPH_TRY(w2.alloc(ctx, (size_t)n));
   PPH_TRY(w3.alloc(ctx, (size_t)n)); PPH_TRY(w4.alloc(ctx, (size_t)n));
-  PPH_HIP(ctx, hipMemcpyAsync(p.p, p_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   int64_t nb = ceil_div64(n, 256);
   const int grid = (int)(nb < 8192 ? nb : 8192);
   const int nzl = (dim == 3) ? m.nzl : 0;
   if (m.kind == PPH_CELL_QUAD)
     hipLaunchKernelGGL(k_darcy_rhs_multilinear<2>, dim3(grid), dim3(256), 0, ctx->stream, m.cells.p, m.cx.p, m.cy.p, m.cz.p,
-                       p.p, conductivity, m.nx, m.ny, nzl, m.px, m.py, n, b.p);
+                       p, conductivity, m.nx, m.ny, nzl, m.px, m.py, n, b.p);
   else if (m.kind == PPH_CELL_HEX)
     hipLaunchKernelGGL(k_darcy_rhs_multilinear<3>, dim3(grid), dim3(256), 0, ctx->stream, m.cells.p, m.cx.p, m.cy.p, m.cz.p,
-                       p.p, conductivity, m.nx, m.ny, nzl, m.px, m.py, n, b.p);
+                       p, conductivity, m.nx, m.ny, nzl, m.px, m.py, n, b.p);
   else if (m.kind == PPH_CELL_TRI)
-    hipLaunchKernelGGL(k_darcy_rhs_simplex<2>, dim3(grid), dim3(256), 0, ctx->stream, m.cells.p, m.cx.p, m.cy.p, m.cz.p, p.p,
+    hipLaunchKernelGGL(k_darcy_rhs_simplex<2>, dim3(grid), dim3(256), 0, ctx->stream, m.cells.p, m.cx.p, m.cy.p, m.cz.p, p,
                        conductivity, m.nx, m.ny, nzl, m.px, m.py, n, b.p);
   else
-    hipLaunchKernelGGL(k_darcy_rhs_simplex<3>, dim3(grid), dim3(256), 0, ctx->stream, m.cells.p, m.cx.p, m.cy.p, m.cz.p, p.p,
+    hipLaunchKernelGGL(k_darcy_rhs_simplex<3>, dim3(grid), dim3(256), 0, ctx->stream, m.cells.p, m.cx.p, m.cy.p, m.cz.p, p,
                        conductivity, m.nx, m.ny, nzl, m.px, m.py, n, b.p);
   PPH_HIP(ctx, hipGetLastError());
   Csr M;
   M.rowptr = m.rowptr.p; M.col = m.col.p; M.val = m.M.p; M.nrows = n; M.nnz = m.nnzb; M.max_row = m.max_row;
   M.lanes = pph_pick_lanes(ctx, M.nnz, M.nrows);
   la_extract_diag_inv(ctx, M, dinv.p);
-  std::vector<double> tmp((size_t)n);
+  std::vector<double> tmp(u_host ? (size_t)n : 0);
   for (int d = 0; d < dim; ++d) {
     int its = 0;
     PPH_TRY(pph_cg_jacobi(ctx, M, b.p + (size_t)d * n, u.p, dinv.p, 1e-13, 0.0, 1000, w1.p, w2.p, w3.p, w4.p, &its));
+    if (u_dev) {
+      hipLaunchKernelGGL(k_interleave, dim3(grid), dim3(256), 0, ctx->stream, u_dev, u.p, d, dim, n);
+      continue;
+    }
     PPH_HIP(ctx, hipMemcpyAsync(tmp.data(), u.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int64_t i = 0; i < n; ++i) u_host[(size_t)i * dim + d] = tmp[(size_t)i];
   }
-  p.release(); b.release(); u.release(); dinv.release(); w1.release(); w2.release(); w3.release(); w4.release();
+  PPH_HIP(ctx, hipGetLastError());
+  // (device output: the work buffers are released - hipFree waits for the interleave launches - and the caller orders its
+  // reads of u_dev after the context stream)
+  b.release(); u.release(); dinv.release(); w1.release(); w2.release(); w3.release(); w4.release();
   return PPH_OK;
+}
+
+extern "C" int pph_darcy_velocity(pph_ctx* ctx, const double* p_host, double conductivity, double* u_host) {
+  if (!ctx) return PPH_ERR_INVALID;
+  PPH_REQUIRE(ctx, ctx->mesh_ok && p_host && u_host, "pph_darcy_velocity: no mesh or NULL buffer");
+  PPH_REQUIRE(ctx, ctx->world == 1, "Darcy velocity projection is implemented for single-context meshes");
+  PPH_HIP(ctx, hipSetDevice(ctx->device));
+  DevBuf<double> p;
+  PPH_TRY(p.alloc(ctx, (size_t)ctx->mesh.n));
+  PPH_HIP(ctx, hipMemcpyAsync(p.p, p_host, sizeof(double) * (size_t)ctx->mesh.n, hipMemcpyHostToDevice, ctx->stream));
+  PPH_TRY(darcy(ctx, p.p, conductivity, u_host, nullptr));
+  p.release();
+  return PPH_OK;
+}
+
+extern "C" int pph_darcy_velocity_device(pph_ctx* ctx, const double* p_dev, double conductivity, double* u_dev) {
+  if (!ctx) return PPH_ERR_INVALID;
+  PPH_REQUIRE(ctx, ctx->mesh_ok && p_dev && u_dev, "pph_darcy_velocity_device: no mesh or NULL buffer");
+  PPH_REQUIRE(ctx, ctx->world == 1, "Darcy velocity projection is implemented for single-context meshes");
+  PPH_HIP(ctx, hipSetDevice(ctx->device));
+  return darcy(ctx, p_dev, conductivity, nullptr, u_dev);
 }

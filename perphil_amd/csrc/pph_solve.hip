@@ -972,6 +972,19 @@ int pph_get_solution(pph_ctx* ctx, double* x_host) {
   return PPH_OK;
 }
 
+// the solution into a caller-owned device buffer, enqueued on the context stream (la_copy: a kernel, not the runtime's
+// device-to-device copy); no synchronisation - the caller orders its own work after the context stream
+int pph_copy_solution_device(pph_ctx* ctx, double* dst, int64_t count) {
+  if (!ctx) return PPH_ERR_INVALID;
+  PPH_REQUIRE(ctx, ctx->asm_ok && ctx->sol.p, "no solution available");
+  PPH_REQUIRE(ctx, dst != nullptr, "dst is NULL");
+  PPH_REQUIRE(ctx, count == 2 * ctx->n, "count %lld, the solution has %lld entries", (long long)count, (long long)(2 * ctx->n));
+  PPH_HIP(ctx, hipSetDevice(ctx->device));
+  la_copy(ctx, dst, ctx->sol.p, count);
+  PPH_HIP(ctx, hipGetLastError());
+  return PPH_OK;
+}
+
 int pph_solve(pph_ctx* ctx, const pph_solver_cfg* cfg, double* x_host, pph_solve_info* info, double* hist,
               int hist_cap) {
   if (!ctx) return PPH_ERR_INVALID;

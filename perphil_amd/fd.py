@@ -12,11 +12,19 @@ reference ``src/perphil/experiments/iterative_bench.py:323-324``).
 from __future__ import annotations
 
 import math
+import sys
 from typing import Callable, Iterable, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
 pi = math.pi
+
+
+def _is_tensor(x) -> bool:
+    """x is a torch.Tensor (without importing torch: no tensor can exist before torch is imported)."""
+    t = sys.modules.get("torch")
+    return t is not None and isinstance(x, t.Tensor)
+
 
 CELL_QUAD, CELL_TRI, CELL_HEX, CELL_TET = 0, 1, 2, 3
 
@@ -233,6 +241,31 @@ class Mesh:
             self._ctx = ctx
         return self._ctx
 
+    def device_index(self) -> int:
+        """The device ``context()`` runs on (or will, when it does not exist yet)."""
+        if self._ctx is not None:
+            return self._ctx.device
+        device = self._dist_args.get("device")
+        if device is not None:
+            return int(device)
+        if self.slab is not None:
+            from .distributed import default_device
+
+            return default_device()
+        return 0
+
+    def _boundary_index(self, device):
+        """(local boundary nodes, the same as an int64 tensor on `device`, their global ids as one): kept per device."""
+        cache = self.__dict__.setdefault("_bnd_index", {})
+        key = str(device)
+        if key not in cache:
+            import torch
+
+            nodes = self.local_boundary_nodes()
+            cache[key] = (nodes, torch.as_tensor(nodes, device=device),
+                          torch.as_tensor(self.local_to_global(nodes), device=device))
+        return cache[key]
+
     def serial_twin(self) -> "Mesh":
         """The same mesh held whole by this process (COMM_SELF): where gathered functions live."""
         if not self.distributed:
@@ -332,9 +365,63 @@ class MixedFunctionSpace:
         return sum(s.local_dim() for s in self._subs)
 
 
+class _Storage:
+    """The coefficients of a Function and of all its views: a host ndarray, or a float64 torch tensor in the memory of the
+    mesh's device.  Device data moves to the host once, on the first host access of any view (the context's pinned result
+    pool takes it when the mesh has one); from then on the host array is authoritative and the tensor is dropped."""
+
+    __slots__ = ("host", "dev", "mesh")
+
+    def __init__(self, host=None, dev=None, mesh=None):
+        self.host, self.dev, self.mesh = host, dev, mesh
+
+    def to_host(self) -> np.ndarray:
+        if self.host is None:
+            from . import _ffi
+
+            self.host = _ffi.tensor_to_host(self.dev, self.mesh._ctx)
+            self.dev = None
+        return self.host
+
+
+class _View:
+    """The slice [off, off + n) of a _Storage that a Function and its ``dat`` read (no reference back to the Function: a
+    dropped Function, and a device result with it, is freed at once, not by the cyclic garbage collector)."""
+
+    __slots__ = ("st", "off", "n", "hv")
+
+    def __init__(self, st: _Storage, off: int, n: int):
+        self.st, self.off, self.n, self.hv = st, off, n, None
+
+    def host(self) -> np.ndarray:
+        v = self.hv
+        if v is None:
+            a = self.st.to_host()
+            v = a if (self.off == 0 and self.n == a.shape[0]) else a[self.off:self.off + self.n]
+            self.hv = v
+        return v
+
+    def owned(self, slab, nfields: int) -> np.ndarray:
+        """Owned entries, field-major (a copy when `slab` is set, the host vector itself otherwise)."""
+        val = self.host()
+        if slab is None:
+            return val
+        nl = slab.n_local
+        return np.concatenate([val[f * nl:(f + 1) * nl][slab.owned_local] for f in range(nfields)])
+
+
 class _Dat:
-    def __init__(self, arr: np.ndarray):
-        self.data = arr
+    def __init__(self, view: _View, slab, nfields: int):
+        self._view, self._slab, self._nf = view, slab, nfields
+        self._owned = None
+
+    @property
+    def data(self):
+        if self._slab is None:
+            return self._view.host()
+        if self._owned is None:
+            self._owned = self._view.owned(self._slab, self._nf)
+        return self._owned
 
     @property
     def data_ro(self):
@@ -346,23 +433,73 @@ class Function:
 
     On a distributed mesh the vector is this rank's LOCAL one (field-major over the slab's box, ghost planes
     included, as the device holds it); ``owned()`` drops the ghost planes, ``gather()`` returns the whole function on
-    the mesh's serial twin on every rank (``dat.data_ro`` is the owned part, as in Firedrake under MPI)."""
+    the mesh's serial twin on every rank (``dat.data_ro`` is the owned part, as in Firedrake under MPI).
 
-    def __init__(self, space, val: Optional[np.ndarray] = None, name: Optional[str] = None):
+    ``val`` may be a NumPy array, a 1-D float64 torch tensor in host memory (shared, not copied) or one on the mesh's
+    device: the function is then DEVICE-RESIDENT (``on_device``) - as the result of a solve is - and its data stay in GPU
+    memory until host code asks for them (``vector()``, ``dat.data``, ``owned()``, ``at()``, ``assign()``,
+    ``interpolate()``, ``gather()``), which moves them to the host once for all views.  ``torch()`` hands the storage to
+    torch code without a copy."""
+
+    def __init__(self, space, val=None, name: Optional[str] = None, _view=None):
         self._space, self.name = space, name
-        n = space.local_dim()
-        if val is None:
-            val = np.zeros(n, dtype=np.float64)
-        if val.shape != (n,):
-            raise ValueError(f"expected {n} coefficients, got {val.shape}")
-        self._val = val
-        self.dat = _Dat(self._val if not space.mesh().distributed else self.owned())
+        mesh = space.mesh()
+        if _view is not None:
+            self._v = _view
+        else:
+            n = space.local_dim()
+            if val is None:
+                val = np.zeros(n, dtype=np.float64)
+            st = None
+            if _is_tensor(val):
+                import torch
+
+                if val.dtype != torch.float64 or val.dim() != 1:
+                    raise ValueError(f"a tensor of coefficients must be 1-D float64, got {val.dtype} of shape {tuple(val.shape)}")
+                if val.is_cuda:
+                    from . import _ffi
+
+                    _ffi.require_shared_runtime("a Function on device data")
+                    if val.device.index != mesh.device_index() or not val.is_contiguous():
+                        raise ValueError(f"device coefficients must be contiguous and on cuda:{mesh.device_index()}, the "
+                                         f"mesh's device (got {val.device})")
+                    if tuple(val.shape) != (n,):
+                        raise ValueError(f"expected {n} coefficients, got {tuple(val.shape)}")
+                    st = _Storage(dev=val.detach(), mesh=mesh)
+                else:
+                    val = val.detach().numpy()        # host tensor: its memory is the array's
+            if st is None:
+                if val.shape != (n,):
+                    raise ValueError(f"expected {n} coefficients, got {val.shape}")
+                st = _Storage(host=val, mesh=mesh)
+            self._v = _View(st, 0, n)
+        self.dat = _Dat(self._v, mesh.slab, len(self._fields()))
 
     def function_space(self):
         return self._space
 
+    @property
+    def on_device(self) -> bool:
+        """True while the coefficients live in GPU memory only."""
+        return self._v.st.dev is not None
+
+    def _host(self) -> np.ndarray:
+        return self._v.host()
+
     def vector(self) -> np.ndarray:
-        return self._val
+        return self._host()
+
+    def torch(self):
+        """The coefficients as a torch tensor, without a copy: a CUDA tensor (a view of the storage) while the function is
+        device-resident, ``torch.from_numpy(vector())`` otherwise.  Torch's current stream is already ordered after the
+        library's writes into it."""
+        v = self._v
+        dev = v.st.dev
+        if dev is None:
+            import torch
+
+            return torch.from_numpy(self.vector())
+        return dev if (v.off == 0 and v.n == dev.shape[0]) else dev[v.off:v.off + v.n]
 
     def _fields(self):
         sp = self._space
@@ -370,11 +507,7 @@ class Function:
 
     def owned(self) -> np.ndarray:
         """Owned entries, field-major (a copy when the mesh is distributed, the vector itself otherwise)."""
-        s = self._space.mesh().slab
-        if s is None:
-            return self._val
-        nl, nf = s.n_local, len(self._fields())
-        return np.concatenate([self._val[f * nl:(f + 1) * nl][s.owned_local] for f in range(nf)])
+        return self._v.owned(self._space.mesh().slab, len(self._fields()))
 
     def gather(self) -> "Function":
         """The whole function on the mesh's serial twin, on every rank (collective; small runs, tests and
@@ -384,7 +517,7 @@ class Function:
             return self
         from .distributed import gather_field_major
 
-        full = gather_field_major(mesh.slab, self._val, mesh._dist_args.get("group"))
+        full = gather_field_major(mesh.slab, self._host(), mesh._dist_args.get("group"))
         twin = mesh.serial_twin()
         fields = self._fields()
         V = FunctionSpace(twin, "CG", 1)
@@ -396,7 +529,7 @@ class Function:
             raise IndexError("not a mixed function")
         off = sum(self._space.sub(k).local_dim() for k in range(i))
         V = self._space.sub(i)
-        return Function(V, self._val[off:off + V.local_dim()], name=f"{self.name or 'w'}[{i}]")
+        return Function(V, name=f"{self.name or 'w'}[{i}]", _view=_View(self._v.st, self._v.off + off, V.local_dim()))
 
     @property
     def subfunctions(self) -> Tuple["Function", ...]:
@@ -406,11 +539,11 @@ class Function:
         return self.subfunctions
 
     def assign(self, other) -> "Function":
-        self._val[:] = other._val if isinstance(other, Function) else float(other)
+        self._host()[:] = other.vector() if isinstance(other, Function) else float(other)
         return self
 
     def interpolate(self, expr) -> "Function":
-        self._val[:] = evaluate(expr, self._space.mesh(), None)
+        self._host()[:] = evaluate(expr, self._space.mesh(), None)
         return self
 
     def at(self, point: Sequence[float]) -> float:
@@ -418,6 +551,10 @@ class Function:
         mesh = self._space.mesh()
         if mesh.distributed:
             return self.gather().at(point)
+        return float(self._host()[self._vertex(point)])
+
+    def _vertex(self, point: Sequence[float]) -> int:
+        mesh = self._space.mesh()
         dims = (mesh.nx, mesh.ny, mesh.nz)[: mesh.dim]
         idx = []
         for c, nc in zip(point, dims):
@@ -426,8 +563,7 @@ class Function:
                 raise NotImplementedError("Function.at is available at mesh vertices only")
             idx.append(int(round(t)))
         px, py, _ = mesh.node_dims
-        node = idx[0] + px * (idx[1] + (py * idx[2] if mesh.dim == 3 else 0))
-        return float(self._val[node])
+        return idx[0] + px * (idx[1] + (py * idx[2] if mesh.dim == 3 else 0))
 
 
 Expr = Union[float, Constant, np.ndarray, Callable[[np.ndarray], np.ndarray], Function]
@@ -443,6 +579,8 @@ def evaluate(expr: Expr, mesh: Mesh, nodes: Optional[np.ndarray]) -> np.ndarray:
         expr = expr.vector()
         if expr.shape != (nloc,):
             raise ValueError("boundary Function must live on a scalar CG-1 space of the same mesh")
+    if _is_tensor(expr):
+        expr = expr.detach().cpu().numpy()   # (host values wanted here; DirichletBC keeps device data on the device)
     if isinstance(expr, (int, float, Constant)):
         return np.full(count, float(expr))
     if isinstance(expr, np.ndarray):
@@ -481,8 +619,15 @@ class DirichletBC:
         conditions used to re-evaluate exp / sin at 394 k boundary nodes (256^3: ~20 ms per field and call).  The cache
         key holds the callable's ``version`` / ``params`` attributes when it has them (MMSPressure: its parameters), so
         a datum whose captured parameters change is evaluated again; ``invalidate()`` drops the cache for callables
-        that change without saying so.  Constants, arrays and Functions are read afresh (they can be reassigned)."""
+        that change without saying so.  Constants, arrays and Functions are read afresh (they can be reassigned).  A CUDA
+        tensor or a device-resident Function is read on the device: nodes and values are then device tensors."""
         mesh = self._V.mesh()
+        dev = self._device_value(mesh)
+        if dev is not None:
+            nodes, nodes_dev, gnodes_dev = mesh._boundary_index(dev.device)
+            if dev.shape[0] == mesh.num_local_vertices():
+                return nodes_dev, dev[nodes_dev]
+            return nodes_dev, dev[gnodes_dev]
         nodes = mesh.local_boundary_nodes()
         if callable(self.value) and not isinstance(self.value, (Function, Constant)):
             key = (id(mesh), id(self.value), getattr(self.value, "version", None), getattr(self.value, "params", None))
@@ -491,6 +636,28 @@ class DirichletBC:
                 self._cache = (key, nodes, evaluate(self.value, mesh, nodes))
             return self._cache[1], self._cache[2]
         return nodes, evaluate(self.value, mesh, nodes)
+
+    def _device_value(self, mesh):
+        """The datum as a device tensor when it lives on the device (a CUDA tensor, a device-resident Function), else None.
+        Device data stay there: nodes_and_values() then returns (int64 node tensor, value tensor) on that device."""
+        v = self.value
+        if isinstance(v, Function):
+            if not v.on_device:
+                return None
+            v = v.torch()
+            if v.shape[0] != mesh.num_local_vertices():
+                raise ValueError("boundary Function must live on a scalar CG-1 space of the same mesh")
+            return v
+        if not (_is_tensor(v) and v.is_cuda):
+            return None
+        from . import _ffi
+
+        _ffi.require_shared_runtime("a DirichletBC with device data")
+        import torch
+
+        if v.dtype != torch.float64 or v.dim() != 1 or v.shape[0] not in (mesh.num_local_vertices(), mesh.num_vertices()):
+            raise ValueError("nodal tensor must be 1-D float64 with one value per mesh vertex (local or global)")
+        return v
 
     def invalidate(self) -> None:
         """Forget the evaluated datum (a callable whose captured state changed)."""

@@ -21,6 +21,9 @@ def split_dpp_solution(dpp_solution: fd.Function) -> Tuple[fd.Function, fd.Funct
     W = dpp_solution.function_space()
     if not hasattr(W, "num_sub_spaces") or W.num_sub_spaces() != 2:
         raise ValueError(f"Expected a 2-field MixedFunctionSpace, got {type(W)}")
+    if dpp_solution.on_device:    # (copies on the device: the parts stay where the solution is)
+        return (fd.Function(W.sub(0), dpp_solution.sub(0).torch().clone(), name="p1_h"),
+                fd.Function(W.sub(1), dpp_solution.sub(1).torch().clone(), name="p2_h"))
     p1 = fd.Function(W.sub(0), dpp_solution.sub(0).vector().copy(), name="p1_h")
     p2 = fd.Function(W.sub(1), dpp_solution.sub(1).vector().copy(), name="p2_h")
     return p1, p2
@@ -35,6 +38,16 @@ def calculate_darcy_velocity_from_pressure(pressure_field: fd.Function, conducti
     Coefficients are node-major: ``u.vector().reshape(-1, dim)[node]`` is the velocity at a vertex.
     """
     mesh = pressure_field.function_space().mesh()
+    if pressure_field.on_device and not mesh.distributed:
+        # device in, device out (pph_darcy_velocity_device)
+        if velocity_space is None:
+            velocity_space = fd.VectorFunctionSpace(mesh, "CG", degree)
+        if velocity_space.degree != 1 or velocity_space.mesh() is not mesh:
+            raise NotImplementedError("the velocity space must be the CG-1 vector space of the pressure's mesh")
+        if not isinstance(conductivity, (int, float, fd.Constant)):
+            raise NotImplementedError("conductivity must be a constant")
+        u = mesh.context().darcy_velocity_device(pressure_field.torch(), float(conductivity))
+        return fd.Function(velocity_space, u, name="velocity")
     if mesh.distributed:
         pressure_field = pressure_field.gather()      # (collective) the projection runs on the serial twin of the mesh
         mesh, velocity_space = pressure_field.function_space().mesh(), None
@@ -54,6 +67,14 @@ def slice_along_x(scalar_field: fd.Function, x_value: float) -> Tuple[np.ndarray
     if mesh.dim != 2:
         raise NotImplementedError("slice_along_x is a 2D utility (as in the reference)")
     y_points = np.arange(mesh.ny + 1) / mesh.ny
+    if scalar_field.on_device:
+        # only the slice's values travel: gathered on the device, then copied
+        import torch
+
+        idx = [scalar_field._vertex((x_value, y)) for y in y_points]
+        t = scalar_field.torch()
+        values = t[torch.as_tensor(idx, device=t.device)].cpu().numpy()
+        return y_points, values
     values = np.array([scalar_field.at((x_value, y)) for y in y_points])
     return y_points, values
 
@@ -62,8 +83,14 @@ def _norms(numerical: fd.Function, exact_expr, quadrature_points: int):
     """Both norms on the device.  `exact_expr` may be what the reference's UFL argument can be: a manufactured pressure
     (closed form evaluated in the kernel), any callable of point arrays `f(X[m, dim]) -> [m]` (optionally with a
     `.grad(X) -> [m, dim]` attribute; central differences otherwise), a CG-1 `Function` on the same mesh, or a
-    `Constant` / number."""
+    `Constant` / number.  A device-resident field is read where it is (no host round trip); on a distributed mesh every
+    rank integrates over the cells it owns and the squared norms are summed over the ranks (no gather) whenever torch
+    shares the library's runtime."""
+    from . import _ffi
+
     mesh = numerical.function_space().mesh()
+    if numerical.on_device or (mesh.distributed and _ffi.shared_runtime()):
+        return _norms_device(numerical, exact_expr, quadrature_points)
     if mesh.distributed:
         # post-processing is not on the sharded path: the whole function on the serial twin of the mesh (collective)
         numerical = numerical.gather()
@@ -88,6 +115,36 @@ def _norms(numerical: fd.Function, exact_expr, quadrature_points: int):
     if callable(exact_expr):
         return ctx.error_norms_sampled(numerical.vector(), exact_expr, getattr(exact_expr, "grad", None), quadrature_points)
     raise TypeError(f"cannot evaluate an exact expression of type {type(exact_expr).__name__}")
+
+
+def _device_field(f: fd.Function, ctx):
+    """The coefficients of `f` as a device tensor (uploaded when the function lives on the host)."""
+    t = f.torch()
+    return t if t.is_cuda else t.to(ctx.torch_device())
+
+
+def _norms_device(numerical: fd.Function, exact_expr, quadrature_points: int, chunk_cells: int = 1 << 16):
+    mesh = numerical.function_space().mesh()
+    ctx = mesh.context()
+    u = _device_field(numerical, ctx)
+    if isinstance(exact_expr, MMSPressure):
+        if exact_expr.dim != mesh.dim:
+            raise ValueError("exact expression and mesh have different dimensions")
+        e = exact_expr
+        return ctx.error_norms_mms_device(e.field, u, e.k1, e.k2, e.beta, e.mu, quadrature_points)
+    if isinstance(exact_expr, fd.Function):
+        if exact_expr.function_space().mesh() is not mesh:
+            raise ValueError("both functions must live on the same mesh")
+        diff = u - _device_field(exact_expr, ctx)     # (the same IEEE subtraction as the host path's)
+        return ctx.error_norms_sampled_device(diff, None, None, min(quadrature_points, 3))
+    if isinstance(exact_expr, (int, float, fd.Constant)):
+        c = float(exact_expr)
+        exact, grad = (lambda X: np.full(X.shape[0], c)), (lambda X: np.zeros_like(X))
+    elif callable(exact_expr):
+        exact, grad = exact_expr, getattr(exact_expr, "grad", None)
+    else:
+        raise TypeError(f"cannot evaluate an exact expression of type {type(exact_expr).__name__}")
+    return ctx.error_norms_sampled_device(u, exact, grad, quadrature_points, chunk_cells=chunk_cells)
 
 
 def l2_error(numerical: fd.Function, exact_expr, quadrature_points: int = 6) -> float:

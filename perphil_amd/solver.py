@@ -43,7 +43,8 @@ _DIRECT_RTOL = 1e-13
 class Solution:
     """Result of a solve (reference solver.py:14-27) + ``info`` with what actually ran.  On a distributed mesh
     ``solution`` holds this rank's slab (``solution.owned()``: its owned rows); ``gather()`` returns the same result
-    with the whole function on every rank."""
+    with the whole function on every rank.  ``solution`` is device-resident (``fd.Function.on_device``) when torch
+    shares the library's HIP runtime: its values reach the host on first host access only."""
     solution: fd.Function | Tuple[fd.Function, fd.Function]
     iteration_number: int
     residual_error: float | np.float64
@@ -192,7 +193,10 @@ def _apply_bcs(ctx: _ffi.Context, W, bcs: List[fd.DirichletBC]) -> None:
     for f in (0, 1):
         nodes, vals = per_field[f]
         if not ctx.same_dirichlet(f, nodes, vals):
-            ctx.set_dirichlet(f, nodes, vals)
+            if isinstance(vals, np.ndarray):
+                ctx.set_dirichlet(f, nodes, vals)
+            else:
+                ctx.set_dirichlet_device(f, nodes, vals)    # (device data: DirichletBC.nodes_and_values)
 
 
 _warned_direct = False
@@ -225,8 +229,14 @@ def _run(W, model_params: DPPParameters, bcs, solver_parameters: Dict, nonlinear
     need_mono = not cfg.picard
     ctx.assemble(float(model_params.k1), float(model_params.k2), float(model_params.beta), float(model_params.mu),
                  monolithic=need_mono)
-    x, sinfo, _ = ctx.solve(cfg, fetch=True)
-    solution = fd.Function(W, x, name="dpp_solution")
+    if _ffi.shared_runtime():
+        # the result stays on the device: copied there into a tensor of torch's allocator (it outlives the next solve and
+        # the context); the host sees it on first access (fd.Function)
+        _, sinfo, _ = ctx.solve(cfg, fetch=False)
+        solution = fd.Function(W, ctx.solution_tensor(), name="dpp_solution")
+    else:
+        x, sinfo, _ = ctx.solve(cfg, fetch=True)
+        solution = fd.Function(W, x, name="dpp_solution")
     info.update(iterations=int(sinfo.iterations), inner_iterations=int(sinfo.inner_iterations),
                 residual=float(sinfo.resnorm), rhs_norm=float(sinfo.rhs_norm), timers=ctx.timers(),
                 converged=bool(sinfo.converged), inner_failed=bool(sinfo.inner_failed))
