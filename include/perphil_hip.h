@@ -16,6 +16,10 @@
  *     outlives pph_ctx_destroy().
  *   - one host thread drives one context (not re-entrant); independent contexts are independent.
  *   - numbering: node (i,j,k) -> i + (nx+1)*(j + (ny+1)*k) inside the LOCAL box of the context;
+ *     degree 2 (pph_mesh_build_lagrange): the nodes are the points of the lattice refined once, node (I,J,K) ->
+ *     I + (2nx+1)*(J + (2ny+1)*K) at (I/2nx, J/2ny, K/2nz); local node order of a cell: Q2 quads / hexes the lattice
+ *     offset (a,b,c) in {0,1,2}^d of the box -> a + 3b (+ 9c); P2 triangles / tetrahedra the cell's CG-1 vertices (in
+ *     the CG-1 dof map's order), then the edge midpoints 01, 02, 12 / 01, 02, 03, 12, 13, 23 (perphil_amd/csrc/pph_p2.h);
  *     monolithic dof = field*n + node (field-major; reference
  *     src/perphil/experiments/iterative_bench.py:323-324).
  *   - all floating point is IEEE fp64; indices are int32 (columns, cell->dof map) / int64 (row
@@ -126,6 +130,12 @@ int pph_ctx_synchronize(pph_ctx* ctx);
  * (multi-GPU cell-slab decomposition); single GPU: whole mesh, no ghosts. */
 int pph_mesh_build(pph_ctx* ctx, int dim, int cell_kind, int nx, int ny, int nz,
                    int z_cell_begin, int z_cell_count, int ghost_lo, int ghost_hi);
+/* Whole mesh (one context, no slabs) with Lagrange pressures of degree 1 or 2 (reference create_function_spaces(mesh,
+ * pressure_deg=...), src/perphil/forms/spaces.py:5-36).  Degree 1 is pph_mesh_build of the whole mesh.  Degree 2: Q2 / P2
+ * nodes on the refined lattice (numbering above; nodes per cell 9 / 6 / 27 / 10); every call below then works on those
+ * nodes, on CSR operators (no stencil-ELL storage, no multigrid hierarchy): a cfg with pc_type mg, or whose field-split /
+ * Picard block solves use mg, returns PPH_ERR_INVALID with a message, and so does pph_darcy_velocity*. */
+int pph_mesh_build_lagrange(pph_ctx* ctx, int dim, int cell_kind, int nx, int ny, int nz, int degree);
 int pph_mesh_sizes(const pph_ctx* ctx, int64_t* n_nodes, int64_t* n_cells, int32_t* nodes_per_cell,
                    int64_t* nnz_block);
 int pph_get_dofmap(pph_ctx* ctx, int32_t* cells_host /* [n_cells][nodes_per_cell] */);

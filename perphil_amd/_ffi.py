@@ -29,7 +29,7 @@ MAT_MONO, MAT_K, MAT_M, MAT_A11, MAT_A22, MAT_A12, MAT_A21 = 0, 1, 2, 3, 4, 5, 6
 # every symbol include/perphil_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "pph_ctx_create", "pph_ctx_destroy", "pph_last_error", "pph_ctx_synchronize",
-    "pph_mesh_build", "pph_mesh_sizes", "pph_get_dofmap", "pph_get_coords",
+    "pph_mesh_build", "pph_mesh_build_lagrange", "pph_mesh_sizes", "pph_get_dofmap", "pph_get_coords",
     "pph_set_dirichlet", "pph_assemble_dpp",
     "pph_solve", "pph_solve_device", "pph_get_solution", "pph_host_alloc", "pph_host_free",
     "pph_csr_sizes", "pph_get_csr", "pph_get_rhs", "pph_spmv", "pph_spmv_bench",
@@ -136,6 +136,7 @@ def _load() -> C.CDLL:
         "pph_last_error": ([p], C.c_char_p),
         "pph_ctx_synchronize": ([p], C.c_int),
         "pph_mesh_build": ([p] + [C.c_int] * 9, C.c_int),
+        "pph_mesh_build_lagrange": ([p] + [C.c_int] * 6, C.c_int),
         "pph_mesh_sizes": ([p, i64p, i64p, i32p, i64p], C.c_int),
         "pph_get_dofmap": ([p, C.c_void_p], C.c_int),
         "pph_get_coords": ([p, C.c_void_p], C.c_int),
@@ -319,6 +320,16 @@ class Context:
         # cells of the device norms (pph_error_norms_*_device): a slab leaves the layer above its lower ghost plane to the
         # neighbour that owns the plane
         self._slab_cells = (self.ncell // z_count if ghost_lo and dim == 3 else 0, self.ncell)
+
+    def mesh_build_lagrange(self, dim: int, kind: int, nx: int, ny: int, nz: int = 0, degree: int = 2) -> None:
+        """Whole mesh with Lagrange nodes of `degree` (1 or 2; degree 2: the lattice refined once, CSR operators only)."""
+        self._check(lib.pph_mesh_build_lagrange(self._h, dim, kind, nx, ny, nz, int(degree)))
+        n, nc, m, nnz = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int64()
+        self._check(lib.pph_mesh_sizes(self._h, C.byref(n), C.byref(nc), C.byref(m), C.byref(nnz)))
+        self.n, self.ncell, self.m, self.nnzb, self.dim = n.value, nc.value, m.value, nnz.value, dim
+        self.degree = int(degree)
+        self._bc_state = {}
+        self._slab_cells = (0, self.ncell)
 
     def dofmap(self) -> np.ndarray:
         out = np.empty((self.ncell, self.m), dtype=np.int32)

@@ -38,20 +38,25 @@ def _set_bcs(ctx, space, bcs: List[fd.DirichletBC]) -> None:
         ctx.set_dirichlet(f, *per_field[f])
 
 
+def _context(space):
+    """The mesh's context for the degree of `space` (mixed: of its first sub space)."""
+    V = space.sub(0) if isinstance(space, fd.MixedFunctionSpace) else space
+    deg = getattr(V, "degree", 1)
+    return space.mesh().context() if deg == 1 else space.mesh().context(degree=deg)
+
+
 def get_matrix_data_from_form(form, boundary_conditions: List[fd.DirichletBC], symmetry_tolerance: float = 1e-8) -> MatrixData:
     """Assemble `form` (monolithic DPP form or one Picard block) with the BCs and export it as SciPy CSR."""
     if form.space.mesh().distributed:
         raise NotImplementedError("matrix export is an analysis path on the whole matrix: build the mesh with "
                                   "comm=fd.COMM_SELF under torch.distributed")
     if isinstance(form, DPPBilinearForm):
-        mesh = form.space.mesh()
-        ctx = mesh.context()
+        ctx = _context(form.space)
         _set_bcs(ctx, form.space, boundary_conditions)
         ctx.assemble(form.k1, form.k2, form.beta, form.mu, monolithic=True)
         csr = ctx.csr(_ffi.MAT_MONO)
     elif isinstance(form, ScalarBlockForm) and form.rank == 2:
-        mesh = form.space.mesh()
-        ctx = mesh.context()
+        ctx = _context(form.space)
         # a scalar block (coef_K K + coef_M M): assemble the pair with the block's coefficients on its own field
         bcs = [fd.DirichletBC(_as_field(bc, form.field), bc.value, bc.sub_domain) for bc in boundary_conditions or []]
         _set_bcs(ctx, form.space, bcs)
@@ -69,7 +74,7 @@ def get_matrix_data_from_form(form, boundary_conditions: List[fd.DirichletBC], s
 
 class _FieldView(fd.FunctionSpace):
     def __init__(self, V, field):
-        super().__init__(V.mesh(), "CG", 1)
+        super().__init__(V.mesh(), "CG", getattr(V, "degree", 1))
         self.index = field
 
 
@@ -82,7 +87,7 @@ def assemble_bilinear_form(form, boundary_conditions: List[fd.DirichletBC]):
     matrix; here: the SciPy CSR exported from the device, explicit zeros of the eliminated pattern kept, like a
     PETSc aij matrix)."""
     if isinstance(form, DPPBilinearForm):
-        ctx = form.space.mesh().context()
+        ctx = _context(form.space)
         _set_bcs(ctx, form.space, boundary_conditions)
         ctx.assemble(form.k1, form.k2, form.beta, form.mu, monolithic=True)
         return csr_matrix(ctx.csr(_ffi.MAT_MONO))

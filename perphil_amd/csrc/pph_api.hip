@@ -214,8 +214,8 @@ __global__ void k_fill_u8(uint8_t* __restrict__ p, uint8_t v, int64_t begin, int
     p[i] |= v;
 }
 
-int pph_mesh_build(pph_ctx* ctx, int dim, int cell_kind, int nx, int ny, int nz, int z_cell_begin, int z_cell_count,
-                   int ghost_lo, int ghost_hi) {
+static int mesh_build(pph_ctx* ctx, int dim, int cell_kind, int nx, int ny, int nz, int z_cell_begin, int z_cell_count,
+                      int ghost_lo, int ghost_hi, int degree) {
   if (!ctx) return PPH_ERR_INVALID;
   PPH_HIP(ctx, hipSetDevice(ctx->device));
   PPH_REQUIRE(ctx, dim == 2 || dim == 3, "dim must be 2 or 3, got %d", dim);
@@ -238,6 +238,7 @@ int pph_mesh_build(pph_ctx* ctx, int dim, int cell_kind, int nx, int ny, int nz,
   ctx->post_u_valid = false;
   PPH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   MeshData& m = ctx->mesh;
+  m.degree = degree;
   m.dim = dim; m.kind = cell_kind; m.nx = nx; m.ny = ny; m.nz = nz; m.z0 = z_cell_begin; m.nzl = z_cell_count;
   ctx->ghost_lo = ghost_lo ? 1 : 0;
   ctx->ghost_hi = ghost_hi ? 1 : 0;
@@ -267,6 +268,18 @@ int pph_mesh_build(pph_ctx* ctx, int dim, int cell_kind, int nx, int ny, int nz,
   PPH_HIP(ctx, hipGetLastError());
   ctx->mesh_ok = true;
   return PPH_OK;
+}
+
+int pph_mesh_build(pph_ctx* ctx, int dim, int cell_kind, int nx, int ny, int nz, int z_cell_begin, int z_cell_count,
+                   int ghost_lo, int ghost_hi) {
+  return mesh_build(ctx, dim, cell_kind, nx, ny, nz, z_cell_begin, z_cell_count, ghost_lo, ghost_hi, 1);
+}
+
+int pph_mesh_build_lagrange(pph_ctx* ctx, int dim, int cell_kind, int nx, int ny, int nz, int degree) {
+  if (!ctx) return PPH_ERR_INVALID;
+  PPH_REQUIRE(ctx, degree == 1 || degree == 2, "Lagrange degree %d: degrees 1 and 2 are implemented", degree);
+  PPH_REQUIRE(ctx, degree == 1 || ctx->world == 1, "degree-2 meshes are single-context meshes (no slab decomposition)");
+  return mesh_build(ctx, dim, cell_kind, nx, ny, dim == 3 ? nz : 0, 0, dim == 3 ? nz : 0, 0, 0, degree);
 }
 
 int pph_mesh_sizes(const pph_ctx* ctx, int64_t* n_nodes, int64_t* n_cells, int32_t* nodes_per_cell,
@@ -467,7 +480,7 @@ static int select_csr(pph_ctx* ctx, int which, Csr* A) {
 
 // scalar-block selectors of pph_spmv / pph_spmv_bench run on a stencil-ELL copy when op_format is 1
 static int attach_sell(pph_ctx* ctx, int which, Csr* A) {
-  if (ctx->op_format != 1 || which == 0) return PPH_OK;
+  if (ctx->op_format != 1 || which == 0 || ctx->mesh.degree != 1) return PPH_OK;   // (degree 2: CSR only)
   if (which >= 3 && ctx->ell_ok) {
     A->ell = (which == 3) ? ctx->S11 : (which == 4) ? ctx->S22 : (which == 5) ? ctx->S12 : ctx->S21;
     return PPH_OK;

@@ -1112,6 +1112,7 @@ __global__ __launch_bounds__(256) void k_asm_simplex_gather(const int32_t* __res
 }
 
 int pph_launch_assemble_KM(pph_ctx* ctx_, MeshData& mesh) {
+  if (mesh.degree == 2) return pph_p2_assemble_KM(ctx_, mesh);
   PPH_TRY(pph_ensure_pattern(ctx_, mesh));
   pph_ctx* ctx = ctx_;
   PPH_TRY(mesh.K.alloc(ctx, (size_t)mesh.nnzb));
@@ -1500,7 +1501,7 @@ int pph_launch_blocks(pph_ctx* ctx, int monolithic) {
   ctx->diag0_valid = false;
   ctx->csr_ok = true;
   ctx->ell_ok = false;
-  if (ctx->op_format == 1) {
+  if (ctx->op_format == 1 && ctx->mesh.degree == 1) {   // (degree 2 has no stencil-ELL storage)
     // the block solves run on stencil-ELL copies (CSR rows of ghost nodes are empty: symmetric storage only without slabs)
     const int sym = pph_sell_sym_from_csr(ctx), sym_c = (sym && ctx->a21_alias) ? 1 : 0;
     PPH_TRY(sell_from_csr(ctx, ctx->mesh, ctx->A11.p, ctx->E11, &ctx->S11, sym));
@@ -2747,7 +2748,7 @@ int pph_mesh_check_affine(pph_ctx* ctx, MeshData& mesh) {
 // (and K, M as well when `asm_keep_km` is set, so that later assemblies with other coefficients reuse them).
 bool pph_can_fuse_assembly(const pph_ctx* ctx) {
   const MeshData& m = ctx->mesh;
-  if (!ctx->asm_fused) return false;
+  if (!ctx->asm_fused || m.degree != 1) return false;   // (degree 2: K and M, then the CSR passes)
   if (m.kind == PPH_CELL_QUAD || m.kind == PPH_CELL_HEX) return ctx->asm_kernel == 2;
   return ctx->asm_kernel != 0;   // simplices: the node-centred gather kernel
 }
@@ -2980,6 +2981,7 @@ int pph_launch_level_operators(pph_ctx* ctx, MeshData& mesh, const uint8_t* m1, 
 }
 
 void pph_launch_row_near(pph_ctx* ctx, const MeshData& mesh, const uint8_t* m1, const uint8_t* m2, uint8_t* out) {
+  if (mesh.degree == 2) { pph_p2_row_near(ctx, mesh, m1, m2, out); return; }
   const int64_t nbn = ceil_div64(mesh.n, 256);
   hipLaunchKernelGGL(k_row_near, dim3((int)(nbn < 4096 ? (nbn < 1 ? 1 : nbn) : 4096)), dim3(256), 0, ctx->stream,
                      make_stencil(mesh.kind), mesh.px, mesh.py, mesh.pzl, m1, m2, mesh.n, out);

@@ -15,14 +15,14 @@
 #include <algorithm>
 
 __global__ __launch_bounds__(256) void k_ilu_levels(int32_t* __restrict__ lev, int64_t nrows, int64_t n, int px, int py,
-                                                    int dim, int fieldoff) {
+                                                    int dim, int fieldoff, int cy, int cz) {
   for (int64_t row = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; row < nrows; row += (int64_t)gridDim.x * blockDim.x) {
     const int64_t node = row % n;
     const int f = (int)(row / n);
     const int i = (int)(node % px);
     const int64_t t = node / px;
     const int j = (int)(t % py), k = (int)(t / py);
-    lev[row] = f * fieldoff + i + 2 * j + ((dim == 3) ? 4 * k : 0);
+    lev[row] = f * fieldoff + i + cy * j + ((dim == 3) ? cz * k : 0);
   }
 }
 
@@ -110,9 +110,12 @@ static int ilu_structure(pph_ctx* ctx, IluData& I, const Csr& A) {
   const int64_t nrows = A.nrows;
   DevBuf<int32_t> lev;
   PPH_TRY(lev.alloc(ctx, (size_t)nrows));
-  const int lmax = m.px + 2 * m.py + ((m.dim == 3) ? 4 * m.pzl : 0);
+  // degree 2 reaches two lattice steps: level i + 3 j + 9 k (every lexicographically lower neighbour within +-2 has
+  // dx + 3 dy + 9 dz <= -1); degree 1: i + 2 j + 4 k
+  const int cy = (m.degree == 2) ? 3 : 2, cz = (m.degree == 2) ? 9 : 4;
+  const int lmax = m.px + cy * m.py + ((m.dim == 3) ? cz * m.pzl : 0);
   hipLaunchKernelGGL(k_ilu_levels, dim3(ilu_grid(nrows, 256)), dim3(256), 0, ctx->stream, lev.p, nrows, m.n, m.px, m.py,
-                     m.dim, lmax + 1);
+                     m.dim, lmax + 1, cy, cz);
   std::vector<int32_t> h((size_t)nrows);
   PPH_HIP(ctx, hipMemcpyAsync(h.data(), lev.p, sizeof(int32_t) * (size_t)nrows, hipMemcpyDeviceToHost, ctx->stream));
   PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));

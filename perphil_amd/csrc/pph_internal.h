@@ -206,6 +206,7 @@ struct Csr {  // device CSR view (no ownership)
 // one structured mesh level (local box): geometry, cell->dof map, scalar pattern, K and M
 struct MeshData {
   int dim = 0, kind = -1, m = 0;        // m = nodes per cell
+  int degree = 1;                       // 2: Q2 / P2 nodes on the lattice refined once (pph_p2.hip); px, py, pzl, n count them
   int nx = 0, ny = 0, nz = 0;           // global cells of this level
   int z0 = 0, nzl = 0;                  // local slab: first cell layer, layer count
   int glo = 0, ghi = 0;                 // lowest / highest local node plane is a ghost plane (owned by a neighbour)
@@ -481,6 +482,13 @@ int pph_launch_mesh(pph_ctx* ctx, MeshData& mesh);
 int pph_launch_pattern(pph_ctx* ctx, int dim, int kind, int px, int py, int pz, DevBuf<int64_t>& rowptr,
                        DevBuf<int32_t>& col, int64_t* nnz_out);
 int pph_launch_assemble_KM(pph_ctx* ctx, MeshData& mesh);
+int pph_scan_counts(pph_ctx* ctx, const int32_t* cnt, int64_t n, DevBuf<int64_t>& rowptr, int64_t* total);
+// degree 2 (pph_p2.hip): sizes, lattice coordinates, cell->dof map and CSR pattern; K and M; rownear from the pattern;
+// reference tables [R_ij (i, j < dim)][a][b] then Mref[a][b]
+int pph_p2_mesh(pph_ctx* ctx, MeshData& mesh);
+int pph_p2_assemble_KM(pph_ctx* ctx, MeshData& mesh);
+void pph_p2_row_near(pph_ctx* ctx, const MeshData& mesh, const uint8_t* m1, const uint8_t* m2, uint8_t* out);
+void pph_p2_tables(int kind, std::vector<double>& tab);
 int pph_ensure_pattern(pph_ctx* ctx, MeshData& mesh);       // scalar CSR pattern on demand (synchronises when it builds)
 int pph_mesh_check_affine(pph_ctx* ctx, MeshData& mesh);   // sets mesh.all_affine (synchronises; mesh build only)
 int pph_launch_blocks(pph_ctx* ctx, int monolithic);

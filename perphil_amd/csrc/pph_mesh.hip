@@ -180,6 +180,22 @@ static int grid_for(int64_t n, int threads = 256, int max_blocks = 2048) {
   return (int)b;
 }
 
+// exclusive scan of n int32 row counts into n + 1 int64 row pointers; *total = the sum (synchronises)
+int pph_scan_counts(pph_ctx* ctx, const int32_t* cnt, int64_t n, DevBuf<int64_t>& rowptr, int64_t* total) {
+  DevBuf<int64_t> sums;
+  const int64_t ntiles = ceil_div64(n, SCAN_TILE);
+  PPH_TRY(sums.alloc(ctx, (size_t)ntiles + 1));
+  PPH_TRY(rowptr.alloc(ctx, (size_t)n + 1));
+  hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)ntiles), dim3(SCAN_THREADS), 0, ctx->stream, cnt, rowptr.p, sums.p, n);
+  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, sums.p, ntiles, sums.p + ntiles);
+  hipLaunchKernelGGL(k_scan_add, dim3(grid_for(n + 1)), dim3(256), 0, ctx->stream, rowptr.p, sums.p, n, sums.p + ntiles);
+  PPH_HIP(ctx, hipMemcpyAsync(total, sums.p + ntiles, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  PPH_HIP(ctx, hipGetLastError());
+  sums.release();
+  return PPH_OK;
+}
+
 int pph_launch_pattern(pph_ctx* ctx, int dim, int kind, int px, int py, int pz, DevBuf<int64_t>& rowptr,
                        DevBuf<int32_t>& col, int64_t* nnz_out) {
   (void)dim;
@@ -215,6 +231,7 @@ int pph_launch_pattern(pph_ctx* ctx, int dim, int kind, int px, int py, int pz, 
 // fills the derived sizes of `mesh` from (dim, kind, nx, ny, nz, z0, nzl) and builds coordinates,
 // cell->dof map and the scalar CSR pattern on the device
 int pph_launch_mesh(pph_ctx* ctx, MeshData& mesh) {
+  if (mesh.degree == 2) return pph_p2_mesh(ctx, mesh);   // (pph_p2.hip)
   mesh.m = (mesh.kind == PPH_CELL_QUAD) ? 4 : (mesh.kind == PPH_CELL_TRI) ? 3 : (mesh.kind == PPH_CELL_HEX) ? 8 : 4;
   mesh.max_row = (mesh.kind == PPH_CELL_QUAD) ? 9 : (mesh.kind == PPH_CELL_TRI) ? 7 : (mesh.kind == PPH_CELL_HEX) ? 27 : 15;
   mesh.px = mesh.nx + 1;

@@ -1,4 +1,4 @@
-// Error norms of a CG-1 field against the manufactured DPP pressures, on the device.
+// Error norms of a CG-1 (or degree-2: k_error_norms_p2) field against the manufactured DPP pressures, on the device.
 //
 // Replaces l2_error / h1_seminorm_error (reference src/perphil/utils/postprocessing.py:89-124, which
 // assemble ||p_h - p||^2 and |p_h - p|_1^2 with Firedrake) for the exact solutions of
@@ -7,6 +7,7 @@
 // onto the simplex (P1 cells); the exact pressure and its gradient are evaluated in closed form at every
 // quadrature point.
 #include "pph_internal.h"
+#include "pph_p2.h"
 #include <cmath>
 
 struct GaussRule {
@@ -306,6 +307,173 @@ __global__ __launch_bounds__(256) void k_error_norms_simplex(const int32_t* __re
   }
 }
 
+// Degree-2 fields (Q2 / P2, pph_p2.h): affine cells, x = X0 + J xi on the reference cell; p_h and its reference gradient
+// from the m nodal values and the degree-2 basis at every point.  Tensor cells: nq-point Gauss rule per direction on
+// [0,1]^d; simplices: the collapsed rule of k_error_norms_simplex.  Same sources (SRC) and partial-sum layout as above.
+template <int KIND, int SRC = 0>
+__global__ __launch_bounds__(256) void k_error_norms_p2(const int32_t* __restrict__ cells, const double* __restrict__ cx,
+                                                        const double* __restrict__ cy, const double* __restrict__ cz,
+                                                        const double* __restrict__ u, GaussRule g, MmsPar p,
+                                                        int64_t ncell, double* __restrict__ part, ErrSamples es = ErrSamples()) {
+  constexpr int DIM = (KIND == PPH_CELL_QUAD || KIND == PPH_CELL_TRI) ? 2 : 3;
+  constexpr bool SIMPLEX = (KIND == PPH_CELL_TRI || KIND == PPH_CELL_TET);
+  constexpr int NB = (KIND == PPH_CELL_QUAD) ? 9 : (KIND == PPH_CELL_TRI) ? 6 : (KIND == PPH_CELL_HEX) ? 27 : 10;
+  __shared__ double lds[4];
+  const double PI = 3.14159265358979323846;
+  double l2 = 0.0, h1 = 0.0;
+  const int64_t cbeg = SRC ? es.c0 : 0, cend = SRC ? es.c1 : ncell;
+  for (int64_t cell = cbeg + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; cell < cend;
+       cell += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t* c = cells + cell * NB;
+    double U[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) U[b] = u[c[b]];
+    double X[DIM + 1][DIM];
+#pragma unroll
+    for (int r = 0; r <= DIM; ++r) {
+      const int32_t nd = c[p2_frame_node(KIND, r)];
+      X[r][0] = cx[nd];
+      X[r][1] = cy[nd];
+      if constexpr (DIM == 3) X[r][2] = cz[nd];
+    }
+    double J[DIM][DIM], I[DIM][DIM], det;   // J[d][e] = X_{e+1}[d] - X_0[d]
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+#pragma unroll
+      for (int e = 0; e < DIM; ++e) J[d][e] = X[e + 1][d] - X[0][d];
+    if constexpr (DIM == 2) {
+      det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+      const double r = 1.0 / det;
+      I[0][0] = J[1][1] * r;  I[0][1] = -J[0][1] * r;
+      I[1][0] = -J[1][0] * r; I[1][1] = J[0][0] * r;
+    } else {
+      const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
+      const double c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
+      const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+      det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
+      const double r = 1.0 / det;
+      I[0][0] = c00 * r;
+      I[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * r;
+      I[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * r;
+      I[1][0] = c01 * r;
+      I[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * r;
+      I[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * r;
+      I[2][0] = c02 * r;
+      I[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * r;
+      I[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * r;
+    }
+    const int nq = g.nq;
+    const int npts = (DIM == 2) ? nq * nq : nq * nq * nq;
+    for (int q = 0; q < npts; ++q) {
+      const int qi[3] = {q % nq, (q / nq) % nq, q / (nq * nq)};
+      double xi[DIM], w;
+      if constexpr (SIMPLEX) {
+        const double uu = 0.5 * (g.x[qi[0]] + 1.0), vv = 0.5 * (g.x[qi[1]] + 1.0);
+        w = 0.25 * g.w[qi[0]] * g.w[qi[1]] * (1.0 - uu);
+        xi[0] = uu;
+        xi[1] = vv * (1.0 - uu);
+        if constexpr (DIM == 3) {
+          const double ww = 0.5 * (g.x[qi[2]] + 1.0);
+          xi[2] = ww * (1.0 - uu) * (1.0 - vv);
+          w *= 0.5 * g.w[qi[2]] * (1.0 - uu) * (1.0 - vv);
+        }
+      } else {
+        w = 1.0;
+#pragma unroll
+        for (int e = 0; e < DIM; ++e) { xi[e] = 0.5 * (g.x[qi[e]] + 1.0); w *= 0.5 * g.w[qi[e]]; }
+      }
+      double uh = 0.0, gr[DIM], xq[DIM];
+#pragma unroll
+      for (int e = 0; e < DIM; ++e) gr[e] = 0.0;
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        double N, dN[DIM];
+        p2_basis<KIND>(b, xi, &N, dN);
+        uh += N * U[b];
+#pragma unroll
+        for (int e = 0; e < DIM; ++e) gr[e] += dN[e] * U[b];
+      }
+#pragma unroll
+      for (int d = 0; d < DIM; ++d) {
+        xq[d] = X[0][d];
+#pragma unroll
+        for (int e = 0; e < DIM; ++e) xq[d] += J[d][e] * xi[e];
+      }
+      double pe = 0.0, ge[DIM];
+#pragma unroll
+      for (int d = 0; d < DIM; ++d) ge[d] = 0.0;
+      if constexpr (SRC == 2) {
+        const int64_t o = ((cell - es.c0) * npts + q) * DIM;
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) es.xout[o + d] = xq[d];
+        continue;
+      } else if constexpr (SRC == 1) {
+        const int64_t o = (cell - es.c0) * npts + q;
+        if (es.se) pe = es.se[o];
+        if (es.sg) {
+#pragma unroll
+          for (int d = 0; d < DIM; ++d) ge[d] = es.sg[o * DIM + d];
+        }
+      } else {
+        const double ex = exp(PI * xq[0]);
+        const double S = sin(PI * xq[1]), Ey = exp(p.eta * xq[1]);
+        if constexpr (DIM == 3) {
+          const double Sz = sin(PI * xq[2]), Ez = exp(p.eta * xq[2]);
+          pe = p.mu_over_pi * ex * (S + Sz) + p.coef_e * (Ey + Ez);
+          ge[0] = p.mu * ex * (S + Sz);
+          ge[1] = p.mu * ex * cos(PI * xq[1]) + p.coef_e * p.eta * Ey;
+          ge[2] = p.mu * ex * cos(PI * xq[2]) + p.coef_e * p.eta * Ez;
+        } else {
+          pe = p.mu_over_pi * ex * S + p.coef_e * Ey;
+          ge[0] = p.mu * ex * S;
+          ge[1] = p.mu * ex * cos(PI * xq[1]) + p.coef_e * p.eta * Ey;
+        }
+      }
+      const double wd = w * fabs(det);
+      const double du = uh - pe;
+      l2 += wd * du * du;
+#pragma unroll
+      for (int d = 0; d < DIM; ++d) {
+        double gh = 0.0;   // (J^-T grad_ref)_d
+#pragma unroll
+        for (int e = 0; e < DIM; ++e) gh += I[e][d] * gr[e];
+        const double dg = gh - ge[d];
+        h1 += wd * dg * dg;
+      }
+    }
+  }
+  auto bsum = [&](double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) lds[wv] = v;
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x == 0) for (int q = 0; q < (int)(blockDim.x >> 6); ++q) t += lds[q];
+    return t;
+  };
+  if constexpr (SRC == 2) return;
+  const double a = bsum(l2);
+  const double b = bsum(h1);
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = a;
+    part[2048 + blockIdx.x] = b;
+  }
+}
+
+template <int SRC>
+static void p2_norms_launch(pph_ctx* ctx, const MeshData& m, const int32_t* cells, const double* u, const GaussRule& g,
+                            const MmsPar& p, int64_t ncell, double* part, ErrSamples es, int grid) {
+  if (m.kind == PPH_CELL_QUAD)
+    hipLaunchKernelGGL((k_error_norms_p2<PPH_CELL_QUAD, SRC>), dim3(grid), dim3(256), 0, ctx->stream, cells, m.cx.p, m.cy.p, m.cz.p, u, g, p, ncell, part, es);
+  else if (m.kind == PPH_CELL_TRI)
+    hipLaunchKernelGGL((k_error_norms_p2<PPH_CELL_TRI, SRC>), dim3(grid), dim3(256), 0, ctx->stream, cells, m.cx.p, m.cy.p, m.cz.p, u, g, p, ncell, part, es);
+  else if (m.kind == PPH_CELL_HEX)
+    hipLaunchKernelGGL((k_error_norms_p2<PPH_CELL_HEX, SRC>), dim3(grid), dim3(256), 0, ctx->stream, cells, m.cx.p, m.cy.p, m.cz.p, u, g, p, ncell, part, es);
+  else
+    hipLaunchKernelGGL((k_error_norms_p2<PPH_CELL_TET, SRC>), dim3(grid), dim3(256), 0, ctx->stream, cells, m.cx.p, m.cy.p, m.cz.p, u, g, p, ncell, part, es);
+}
+
 __global__ __launch_bounds__(256) void k_sum_partials(const double* __restrict__ part, int nblocks, double* __restrict__ out) {
   __shared__ double lds[256];
   const double* p = part + (int64_t)blockIdx.x * 2048;
@@ -386,7 +554,9 @@ static int norms_mms(pph_ctx* ctx, int field, const double* u, int64_t c0, int64
   int64_t nb = ceil_div64(count, 256);
   const int grid = (int)(nb < 2048 ? nb : 2048);
   const int32_t* cells = m.cells.p + c0 * m.m;   // (the closed-form source reads no per-cell samples: a cell range is an offset)
-  if (m.kind == PPH_CELL_QUAD)
+  if (m.degree == 2)
+    p2_norms_launch<0>(ctx, m, cells, u, g, p, count, part.p, ErrSamples(), grid);
+  else if (m.kind == PPH_CELL_QUAD)
     hipLaunchKernelGGL(k_error_norms<2>, dim3(grid), dim3(256), 0, ctx->stream, cells, m.cx.p, m.cy.p, m.cz.p, u, g,
                        p, count, part.p);
   else if (m.kind == PPH_CELL_TRI)
@@ -451,6 +621,7 @@ extern "C" int pph_error_norms_mms_device(pph_ctx* ctx, int field, const double*
 template <int SRC>
 static void err_launch(pph_ctx* ctx, const MeshData& m, const double* u, const GaussRule& g, double* part, ErrSamples es, int grid) {
   MmsPar p = MmsPar();
+  if (m.degree == 2) { p2_norms_launch<SRC>(ctx, m, m.cells.p, u, g, p, m.ncell, part, es, grid); return; }
   if (m.kind == PPH_CELL_QUAD)
     hipLaunchKernelGGL((k_error_norms<2, SRC>), dim3(grid), dim3(256), 0, ctx->stream, m.cells.p, m.cx.p, m.cy.p, m.cz.p, u, g, p, m.ncell, part, es);
   else if (m.kind == PPH_CELL_TRI)
@@ -831,6 +1002,7 @@ static int darcy(pph_ctx* ctx, const double* p, double conductivity, double* u_h
 extern "C" int pph_darcy_velocity(pph_ctx* ctx, const double* p_host, double conductivity, double* u_host) {
   if (!ctx) return PPH_ERR_INVALID;
   PPH_REQUIRE(ctx, ctx->mesh_ok && p_host && u_host, "pph_darcy_velocity: no mesh or NULL buffer");
+  PPH_REQUIRE(ctx, ctx->mesh.degree == 1, "Darcy velocity of a degree-2 pressure is not implemented");
   PPH_REQUIRE(ctx, ctx->world == 1, "Darcy velocity projection is implemented for single-context meshes");
   PPH_HIP(ctx, hipSetDevice(ctx->device));
   DevBuf<double> p;
@@ -844,6 +1016,7 @@ extern "C" int pph_darcy_velocity(pph_ctx* ctx, const double* p_host, double con
 extern "C" int pph_darcy_velocity_device(pph_ctx* ctx, const double* p_dev, double conductivity, double* u_dev) {
   if (!ctx) return PPH_ERR_INVALID;
   PPH_REQUIRE(ctx, ctx->mesh_ok && p_dev && u_dev, "pph_darcy_velocity_device: no mesh or NULL buffer");
+  PPH_REQUIRE(ctx, ctx->mesh.degree == 1, "Darcy velocity of a degree-2 pressure is not implemented");
   PPH_REQUIRE(ctx, ctx->world == 1, "Darcy velocity projection is implemented for single-context meshes");
   PPH_HIP(ctx, hipSetDevice(ctx->device));
   return darcy(ctx, p_dev, conductivity, nullptr, u_dev);

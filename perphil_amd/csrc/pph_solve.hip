@@ -688,6 +688,11 @@ static int validate_cfg(pph_ctx* ctx, const pph_solver_cfg* cfg) {
   PPH_REQUIRE(ctx, cfg->ksp_type >= PPH_KSP_PREONLY && cfg->ksp_type <= PPH_KSP_GMRES, "unknown ksp_type %d",
               cfg->ksp_type);
   PPH_REQUIRE(ctx, cfg->pc_type >= PPH_PC_NONE && cfg->pc_type <= PPH_PC_ILU, "unknown pc_type %d", cfg->pc_type);
+  // degree 2 has no multigrid hierarchy: pc mg, and block solves on it (which the LU blocks also stand for), are refused
+  PPH_REQUIRE(ctx, ctx->mesh.degree == 1 || (cfg->pc_type != PPH_PC_MG &&
+                   !((cfg->pc_type == PPH_PC_FIELDSPLIT || cfg->picard) && cfg->inner_pc_type == PPH_PC_MG)),
+              "degree-2 spaces have no multigrid hierarchy: pc_type mg (also as the block pc of a field split / Picard sweep, "
+              "and the LU blocks it stands for) is not available; use none, jacobi, pph_block2 or ilu");
   PPH_REQUIRE(ctx, !(cfg->pc_type == PPH_PC_ILU || cfg->inner_pc_type == PPH_PC_ILU) || ctx->world == 1,
               "pc_type ilu eliminates sequentially along the global row order: single context only");
   PPH_REQUIRE(ctx, cfg->restart >= 1 && cfg->restart <= 30, "GMRES restart %d outside [1,30]", cfg->restart);

@@ -7,7 +7,9 @@ boundary data); all arithmetic happens in the HIP library behind ``perphil_amd._
 
 Numbering (documented, differs from Firedrake's DMPlex numbering which cannot be reproduced):
 node (i,j,k) -> i + (nx+1)*(j + (ny+1)*k); mixed dof = field*n + node (field-major, as pinned by
-reference ``src/perphil/experiments/iterative_bench.py:323-324``).
+reference ``src/perphil/experiments/iterative_bench.py:323-324``).  Degree-2 spaces (Q2 / P2) number the points of
+the lattice refined once the same way: (I,J,K) -> I + (2nx+1)*(J + (2ny+1)*K) at (I/2nx, J/2ny, K/2nz); they live on
+the mesh's degree-2 context (``Mesh.context(degree=2)``) and are never distributed.
 """
 from __future__ import annotations
 
@@ -151,6 +153,16 @@ class Mesh:
     def node_dims(self) -> Tuple[int, int, int]:
         return self.nx + 1, self.ny + 1, (self.nz + 1 if self.dim == 3 else 1)
 
+    def lattice_dims(self, degree: int = 1) -> Tuple[int, int, int]:
+        """Nodes per direction of the degree-`degree` Lagrange space (degree 2: the lattice refined once)."""
+        if degree == 1:
+            return self.node_dims
+        return 2 * self.nx + 1, 2 * self.ny + 1, (2 * self.nz + 1 if self.dim == 3 else 1)
+
+    def num_nodes(self, degree: int = 1) -> int:
+        px, py, pz = self.lattice_dims(degree)
+        return px * py * pz
+
     def num_vertices(self) -> int:
         """Global vertex count (like Firedrake's under MPI)."""
         px, py, pz = self.node_dims
@@ -174,25 +186,27 @@ class Mesh:
         return nodes if s is None else nodes + s.z_begin * s.plane
 
     # -- geometry (host side, closed form; only boundary coordinates are needed by the hot path) --
-    def node_coordinates(self, nodes: Optional[np.ndarray] = None) -> np.ndarray:
-        """Coordinates of GLOBAL vertex ids (all vertices if None)."""
-        px, py, _ = self.node_dims
-        ids = np.arange(self.num_vertices(), dtype=np.int64) if nodes is None else np.asarray(nodes, dtype=np.int64)
+    def node_coordinates(self, nodes: Optional[np.ndarray] = None, degree: int = 1) -> np.ndarray:
+        """Coordinates of GLOBAL vertex ids (all vertices if None); degree 2: of the lattice nodes."""
+        px, py, _ = self.lattice_dims(degree)
+        ids = np.arange(self.num_nodes(degree), dtype=np.int64) if nodes is None else np.asarray(nodes, dtype=np.int64)
         i, j = ids % px, (ids // px) % py
-        cols = [i / self.nx, j / self.ny]
+        cols = [i / (degree * self.nx), j / (degree * self.ny)]
         if self.dim == 3:
-            cols.append((ids // (px * py)) / self.nz)
+            cols.append((ids // (px * py)) / (degree * self.nz))
         return np.stack(cols, axis=1).astype(np.float64)
 
-    def local_node_coordinates(self, nodes: Optional[np.ndarray] = None) -> np.ndarray:
-        """Coordinates of LOCAL vertex ids (all local vertices if None)."""
+    def local_node_coordinates(self, nodes: Optional[np.ndarray] = None, degree: int = 1) -> np.ndarray:
+        """Coordinates of LOCAL vertex ids (all local vertices if None); degree-2 nodes are never distributed."""
+        if degree != 1:
+            return self.node_coordinates(nodes, degree)
         if nodes is None:
             nodes = np.arange(self.num_local_vertices(), dtype=np.int64)
         return self.node_coordinates(self.local_to_global(nodes))
 
-    def boundary_nodes(self) -> np.ndarray:
-        """Sorted GLOBAL vertex ids with the "on_boundary" marker."""
-        px, py, pz = self.node_dims
+    def boundary_nodes(self, degree: int = 1) -> np.ndarray:
+        """Sorted GLOBAL vertex ids (degree 2: lattice node ids) with the "on_boundary" marker."""
+        px, py, pz = self.lattice_dims(degree)
         if self.dim == 2:
             m = np.zeros((py, px), dtype=bool)
             m[0, :] = m[-1, :] = True
@@ -204,17 +218,22 @@ class Mesh:
             m[:, :, 0] = m[:, :, -1] = True
         return np.nonzero(m.ravel())[0].astype(np.int64)
 
-    def local_boundary_nodes(self) -> np.ndarray:
+    def local_boundary_nodes(self, degree: int = 1) -> np.ndarray:
         """Sorted LOCAL vertex ids on the boundary of the unit square / cube (ghost planes included: their Dirichlet
         values enter the lifting of the owned rows next to them)."""
+        if degree != 1:
+            return self.boundary_nodes(degree)
         s = self.slab
         return self.boundary_nodes() if s is None else s.boundary_local()[0]
 
-    def context(self, device: Optional[int] = None):
+    def context(self, device: Optional[int] = None, degree: int = 1):
         """Device context holding this mesh - this rank's slab with its transport when the mesh is distributed
-        (cell->dof map, operators and the multigrid hierarchy are cached there)."""
+        (cell->dof map, operators and the multigrid hierarchy are cached there).  ``degree=2``: the context of the
+        degree-2 nodes (whole mesh, CSR operators), cached per device next to the CG-1 one and independent of it."""
         from . import _ffi
 
+        if degree != 1:
+            return self._lagrange_context(device, degree)
         s = self.slab
         if device is None:
             device = self._dist_args.get("device")
@@ -241,6 +260,23 @@ class Mesh:
             self._ctx = ctx
         return self._ctx
 
+    def _lagrange_context(self, device: Optional[int], degree: int):
+        from . import _ffi
+
+        if degree != 2:
+            raise NotImplementedError(f"Lagrange degree {degree}: degrees 1 and 2 are implemented")
+        if self.distributed:
+            raise NotImplementedError("degree-2 spaces are not distributed: build the mesh with comm=fd.COMM_SELF")
+        if device is None:
+            device = self.device_index()
+        cache = self.__dict__.setdefault("_ctx_deg", {})
+        ctx = cache.get((degree, device))
+        if ctx is None:
+            ctx = _ffi.Context(device)
+            ctx.mesh_build_lagrange(self.dim, self.kind, self.nx, self.ny, self.nz, degree)
+            cache[(degree, device)] = ctx
+        return ctx
+
     def device_index(self) -> int:
         """The device ``context()`` runs on (or will, when it does not exist yet)."""
         if self._ctx is not None:
@@ -254,16 +290,17 @@ class Mesh:
             return default_device()
         return 0
 
-    def _boundary_index(self, device):
-        """(local boundary nodes, the same as an int64 tensor on `device`, their global ids as one): kept per device."""
+    def _boundary_index(self, device, degree: int = 1):
+        """(local boundary nodes, the same as an int64 tensor on `device`, their global ids as one): kept per device and
+        degree."""
         cache = self.__dict__.setdefault("_bnd_index", {})
-        key = str(device)
+        key = str(device) if degree == 1 else (str(device), degree)
         if key not in cache:
             import torch
 
-            nodes = self.local_boundary_nodes()
-            cache[key] = (nodes, torch.as_tensor(nodes, device=device),
-                          torch.as_tensor(self.local_to_global(nodes), device=device))
+            nodes = self.local_boundary_nodes(degree)
+            glob = self.local_to_global(nodes) if degree == 1 else nodes
+            cache[key] = (nodes, torch.as_tensor(nodes, device=device), torch.as_tensor(glob, device=device))
         return cache[key]
 
     def serial_twin(self) -> "Mesh":
@@ -287,12 +324,13 @@ def UnitCubeMesh(nx: int, ny: int, nz: int, hexahedral: bool = False, comm=COMM_
 
 
 class FunctionSpace:
-    """CG-1 scalar space: one dof per mesh vertex."""
+    """Continuous Lagrange scalar space: CG-1 (one dof per mesh vertex) or CG-2 (Q2 / P2: one dof per point of the
+    lattice refined once, see the module docstring)."""
 
     def __init__(self, mesh: Mesh, family: str = "CG", degree: int = 1, name: Optional[str] = None):
-        if family not in ("CG", "Lagrange", "P", "Q") or degree != 1:
-            raise NotImplementedError("the MI355X path implements the conforming CG-1 pressure space only")
-        self._mesh, self.family, self.degree, self.name = mesh, "CG", 1, name
+        if family not in ("CG", "Lagrange", "P", "Q") or degree not in (1, 2):
+            raise NotImplementedError("the MI355X path implements the conforming CG-1 and CG-2 pressure spaces only")
+        self._mesh, self.family, self.degree, self.name = mesh, "CG", int(degree), name
         self.index: Optional[int] = None
         self.parent: Optional["MixedFunctionSpace"] = None
 
@@ -301,11 +339,12 @@ class FunctionSpace:
 
     def dim(self) -> int:
         """Global dof count (what Firedrake's ``V.dim()`` reports under MPI as well)."""
-        return self._mesh.num_vertices()
+        return self._mesh.num_vertices() if self.degree == 1 else self._mesh.num_nodes(self.degree)
 
     def local_dim(self) -> int:
-        """Dofs this rank stores (owned + ghost planes of its slab); = dim() when the mesh is not distributed."""
-        return self._mesh.num_local_vertices()
+        """Dofs this rank stores (owned + ghost planes of its slab); = dim() when the mesh is not distributed (and for
+        degree 2, which is never distributed)."""
+        return self._mesh.num_local_vertices() if self.degree == 1 else self._mesh.num_nodes(self.degree)
 
     def num_sub_spaces(self) -> int:
         return 1
@@ -318,6 +357,8 @@ class VectorFunctionSpace(FunctionSpace):
     """CG-1 vector space (velocity space U of ``create_function_spaces``; not on the hot path)."""
 
     def __init__(self, mesh: Mesh, family: str = "CG", degree: int = 1, name: Optional[str] = None):
+        if degree != 1:
+            raise NotImplementedError("the MI355X path implements the CG-1 vector space only")
         super().__init__(mesh, family, degree, name)
         self.value_size = mesh.dim
 
@@ -543,11 +584,12 @@ class Function:
         return self
 
     def interpolate(self, expr) -> "Function":
-        self._host()[:] = evaluate(expr, self._space.mesh(), None)
+        self._host()[:] = evaluate(expr, self._space.mesh(), None, getattr(self._space, "degree", 1))
         return self
 
     def at(self, point: Sequence[float]) -> float:
-        """Value at a point that coincides with a mesh vertex (what ``slice_along_x`` needs)."""
+        """Value at a point that coincides with a mesh vertex (what ``slice_along_x`` needs); on a degree-2 space at
+        any node of its lattice."""
         mesh = self._space.mesh()
         if mesh.distributed:
             return self.gather().at(point)
@@ -555,30 +597,31 @@ class Function:
 
     def _vertex(self, point: Sequence[float]) -> int:
         mesh = self._space.mesh()
-        dims = (mesh.nx, mesh.ny, mesh.nz)[: mesh.dim]
+        deg = getattr(self._space, "degree", 1)
+        dims = (deg * mesh.nx, deg * mesh.ny, deg * mesh.nz)[: mesh.dim]
         idx = []
         for c, nc in zip(point, dims):
             t = c * nc
             if abs(t - round(t)) > 1e-9:
-                raise NotImplementedError("Function.at is available at mesh vertices only")
+                raise NotImplementedError("Function.at is available at the nodes of the space only")
             idx.append(int(round(t)))
-        px, py, _ = mesh.node_dims
+        px, py, _ = mesh.lattice_dims(deg)
         return idx[0] + px * (idx[1] + (py * idx[2] if mesh.dim == 3 else 0))
 
 
 Expr = Union[float, Constant, np.ndarray, Callable[[np.ndarray], np.ndarray], Function]
 
 
-def evaluate(expr: Expr, mesh: Mesh, nodes: Optional[np.ndarray]) -> np.ndarray:
+def evaluate(expr: Expr, mesh: Mesh, nodes: Optional[np.ndarray], degree: int = 1) -> np.ndarray:
     """Values of a boundary/initial datum at the LOCAL mesh vertices ``nodes`` (all local vertices if None; local =
     global on a mesh that is not distributed).  Callables see global coordinates; nodal arrays may be global (one value
-    per mesh vertex) or local; Functions are read where they live."""
-    nloc = mesh.num_local_vertices()
+    per mesh vertex) or local; Functions are read where they live.  ``degree=2``: at the nodes of the degree-2 lattice."""
+    nloc = mesh.num_local_vertices() if degree == 1 else mesh.num_nodes(degree)
     count = nloc if nodes is None else len(nodes)
     if isinstance(expr, Function):
         expr = expr.vector()
         if expr.shape != (nloc,):
-            raise ValueError("boundary Function must live on a scalar CG-1 space of the same mesh")
+            raise ValueError("boundary Function must live on a scalar space of the same mesh and degree")
     if _is_tensor(expr):
         expr = expr.detach().cpu().numpy()   # (host values wanted here; DirichletBC keeps device data on the device)
     if isinstance(expr, (int, float, Constant)):
@@ -586,12 +629,12 @@ def evaluate(expr: Expr, mesh: Mesh, nodes: Optional[np.ndarray]) -> np.ndarray:
     if isinstance(expr, np.ndarray):
         if expr.shape == (nloc,):
             return expr if nodes is None else expr[nodes]
-        if expr.shape == (mesh.num_vertices(),):
+        if degree == 1 and expr.shape == (mesh.num_vertices(),):
             g = mesh.local_to_global(np.arange(nloc, dtype=np.int64) if nodes is None else nodes)
             return expr[g]
         raise ValueError("nodal array must have one value per mesh vertex")
     if callable(expr):
-        vals = np.asarray(expr(mesh.local_node_coordinates(nodes)), dtype=np.float64)
+        vals = np.asarray(expr(mesh.local_node_coordinates(nodes, degree)), dtype=np.float64)
         if vals.shape != (count,):
             raise ValueError("expression must return one value per point")
         return vals
@@ -622,20 +665,25 @@ class DirichletBC:
         that change without saying so.  Constants, arrays and Functions are read afresh (they can be reassigned).  A CUDA
         tensor or a device-resident Function is read on the device: nodes and values are then device tensors."""
         mesh = self._V.mesh()
+        deg = getattr(self._V, "degree", 1)
         dev = self._device_value(mesh)
         if dev is not None:
-            nodes, nodes_dev, gnodes_dev = mesh._boundary_index(dev.device)
-            if dev.shape[0] == mesh.num_local_vertices():
+            nodes, nodes_dev, gnodes_dev = mesh._boundary_index(dev.device, deg)
+            if dev.shape[0] == self._nloc(mesh):
                 return nodes_dev, dev[nodes_dev]
             return nodes_dev, dev[gnodes_dev]
-        nodes = mesh.local_boundary_nodes()
+        nodes = mesh.local_boundary_nodes(deg)
         if callable(self.value) and not isinstance(self.value, (Function, Constant)):
-            key = (id(mesh), id(self.value), getattr(self.value, "version", None), getattr(self.value, "params", None))
+            key = (id(mesh), id(self.value), getattr(self.value, "version", None), getattr(self.value, "params", None), deg)
             cached = getattr(self, "_cache", None)
             if cached is None or cached[0] != key:
-                self._cache = (key, nodes, evaluate(self.value, mesh, nodes))
+                self._cache = (key, nodes, evaluate(self.value, mesh, nodes, deg))
             return self._cache[1], self._cache[2]
-        return nodes, evaluate(self.value, mesh, nodes)
+        return nodes, evaluate(self.value, mesh, nodes, deg)
+
+    def _nloc(self, mesh) -> int:
+        deg = getattr(self._V, "degree", 1)
+        return mesh.num_local_vertices() if deg == 1 else mesh.num_nodes(deg)
 
     def _device_value(self, mesh):
         """The datum as a device tensor when it lives on the device (a CUDA tensor, a device-resident Function), else None.
@@ -645,8 +693,8 @@ class DirichletBC:
             if not v.on_device:
                 return None
             v = v.torch()
-            if v.shape[0] != mesh.num_local_vertices():
-                raise ValueError("boundary Function must live on a scalar CG-1 space of the same mesh")
+            if v.shape[0] != self._nloc(mesh):
+                raise ValueError("boundary Function must live on a scalar space of the same mesh and degree")
             return v
         if not (_is_tensor(v) and v.is_cuda):
             return None
@@ -655,7 +703,8 @@ class DirichletBC:
         _ffi.require_shared_runtime("a DirichletBC with device data")
         import torch
 
-        if v.dtype != torch.float64 or v.dim() != 1 or v.shape[0] not in (mesh.num_local_vertices(), mesh.num_vertices()):
+        nglob = mesh.num_vertices() if getattr(self._V, "degree", 1) == 1 else self._nloc(mesh)
+        if v.dtype != torch.float64 or v.dim() != 1 or v.shape[0] not in (self._nloc(mesh), nglob):
             raise ValueError("nodal tensor must be 1-D float64 with one value per mesh vertex (local or global)")
         return v
 

@@ -38,6 +38,8 @@ def calculate_darcy_velocity_from_pressure(pressure_field: fd.Function, conducti
     Coefficients are node-major: ``u.vector().reshape(-1, dim)[node]`` is the velocity at a vertex.
     """
     mesh = pressure_field.function_space().mesh()
+    if getattr(pressure_field.function_space(), "degree", 1) != 1:
+        raise NotImplementedError("the Darcy velocity of a degree-2 pressure is not implemented")
     if pressure_field.on_device and not mesh.distributed:
         # device in, device out (pph_darcy_velocity_device)
         if velocity_space is None:
@@ -97,7 +99,7 @@ def _norms(numerical: fd.Function, exact_expr, quadrature_points: int):
         if isinstance(exact_expr, fd.Function):
             exact_expr = exact_expr.gather()
         mesh = numerical.function_space().mesh()
-    ctx = mesh.context()
+    ctx = _context(numerical)
     if isinstance(exact_expr, MMSPressure):
         if exact_expr.dim != mesh.dim:
             raise ValueError("exact expression and mesh have different dimensions")
@@ -107,7 +109,7 @@ def _norms(numerical: fd.Function, exact_expr, quadrature_points: int):
         if exact_expr.function_space().mesh() is not mesh:
             raise ValueError("both functions must live on the same mesh")
         diff = np.asarray(numerical.vector(), dtype=np.float64) - np.asarray(exact_expr.vector(), dtype=np.float64)
-        return ctx.error_norms_sampled(diff, None, None, min(quadrature_points, 3))   # CG-1 difference: exact with 2-3 points
+        return ctx.error_norms_sampled(diff, None, None, min(quadrature_points, _exact_points(numerical)))
     if isinstance(exact_expr, (int, float, fd.Constant)):
         c = float(exact_expr)
         return ctx.error_norms_sampled(numerical.vector(), lambda X: np.full(X.shape[0], c), lambda X: np.zeros_like(X),
@@ -115,6 +117,19 @@ def _norms(numerical: fd.Function, exact_expr, quadrature_points: int):
     if callable(exact_expr):
         return ctx.error_norms_sampled(numerical.vector(), exact_expr, getattr(exact_expr, "grad", None), quadrature_points)
     raise TypeError(f"cannot evaluate an exact expression of type {type(exact_expr).__name__}")
+
+
+def _context(f: fd.Function):
+    """The context of the space `f` lives on (the mesh's CG-1 one, or its degree-2 one)."""
+    V = f.function_space()
+    deg = getattr(V, "degree", 1)
+    return V.mesh().context() if deg == 1 else V.mesh().context(degree=deg)
+
+
+def _exact_points(f: fd.Function) -> int:
+    """Points per direction that integrate the norms of a difference of two functions of f's space exactly: 2-3 for
+    CG-1; 3 (Q2) / 4 (P2 on the collapsed rule) for degree 2."""
+    return 3 if getattr(f.function_space(), "degree", 1) == 1 else 4
 
 
 def _device_field(f: fd.Function, ctx):
@@ -125,7 +140,7 @@ def _device_field(f: fd.Function, ctx):
 
 def _norms_device(numerical: fd.Function, exact_expr, quadrature_points: int, chunk_cells: int = 1 << 16):
     mesh = numerical.function_space().mesh()
-    ctx = mesh.context()
+    ctx = _context(numerical)
     u = _device_field(numerical, ctx)
     if isinstance(exact_expr, MMSPressure):
         if exact_expr.dim != mesh.dim:
@@ -136,7 +151,7 @@ def _norms_device(numerical: fd.Function, exact_expr, quadrature_points: int, ch
         if exact_expr.function_space().mesh() is not mesh:
             raise ValueError("both functions must live on the same mesh")
         diff = u - _device_field(exact_expr, ctx)     # (the same IEEE subtraction as the host path's)
-        return ctx.error_norms_sampled_device(diff, None, None, min(quadrature_points, 3))
+        return ctx.error_norms_sampled_device(diff, None, None, min(quadrature_points, _exact_points(numerical)))
     if isinstance(exact_expr, (int, float, fd.Constant)):
         c = float(exact_expr)
         exact, grad = (lambda X: np.full(X.shape[0], c)), (lambda X: np.zeros_like(X))

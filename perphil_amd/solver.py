@@ -199,6 +199,20 @@ def _apply_bcs(ctx: _ffi.Context, W, bcs: List[fd.DirichletBC]) -> None:
                 ctx.set_dirichlet_device(f, nodes, vals)    # (device data: DirichletBC.nodes_and_values)
 
 
+def degree2_unsupported(cfg: _ffi.SolverCfg, info: dict) -> Optional[str]:
+    """Why a translated configuration cannot run on a degree-2 space (no multigrid hierarchy there), or None."""
+    if info.get("direct_equivalent"):
+        return "ksp_type preonly + pc_type lu runs as field-split GMRES with multigrid-CG block solves"
+    if cfg.pc_type == _ffi.PC_MG:
+        return "pc_type mg needs the multigrid hierarchy"
+    if (cfg.pc_type == _ffi.PC_FIELDSPLIT or cfg.picard) and cfg.inner_pc_type == _ffi.PC_MG:
+        what = "Picard" if cfg.picard else "field-split"
+        if cfg.inner_exact:
+            return f"{what} blocks with pc_type lu run as multigrid-CG block solves"
+        return f"{what} blocks with pc_type mg need the multigrid hierarchy"
+    return None
+
+
 _warned_direct = False
 
 
@@ -207,8 +221,18 @@ def _run(W, model_params: DPPParameters, bcs, solver_parameters: Dict, nonlinear
     global _warned_direct
     cfg, info = translate_options(solver_parameters, nonlinear=nonlinear)
     mesh = W.mesh()
-    # this rank's slab + its transport when the mesh is distributed (fd.Mesh); the solver loops are the same
-    ctx = mesh.context(device)
+    degree = getattr(W.sub(0), "degree", 1)
+    if degree != 1:
+        # checked before any context exists: a refusal never touches a GPU
+        why = degree2_unsupported(cfg, info)
+        if why is not None:
+            raise NotImplementedError(f"degree-{degree} spaces have no multigrid hierarchy: {why} (use e.g. GMRES + ILU)")
+        if mesh.dim == 3 and mesh.distributed:
+            raise NotImplementedError("degree-2 spaces are not distributed: build the mesh with comm=fd.COMM_SELF")
+        ctx = mesh.context(device, degree=degree)
+    else:
+        # this rank's slab + its transport when the mesh is distributed (fd.Mesh); the solver loops are the same
+        ctx = mesh.context(device)
     if mesh.distributed:
         if cfg.pc_type == _ffi.PC_ILU or (cfg.inner_pc_type == _ffi.PC_ILU and cfg.pc_type == _ffi.PC_FIELDSPLIT):
             raise NotImplementedError("pc_type ilu is a sequential-elimination preconditioner: not available on a "
