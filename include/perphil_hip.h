@@ -60,8 +60,14 @@ enum {
   PPH_PC_BLOCK2 = 2,      /* 2x2 node-block Jacobi (both pressures of one node coupled)    */
   PPH_PC_FIELDSPLIT = 3,  /* pc_type fieldsplit, pc_fieldsplit_type multiplicative         */
   PPH_PC_MG = 4,          /* geometric multigrid V-cycle (scalar blocks; inside fieldsplit/Picard) */
-  PPH_PC_ILU = 5          /* pc_type ilu, pc_factor_levels 0: ILU(0) in the natural row order, level-scheduled
+  PPH_PC_ILU = 5,         /* pc_type ilu, pc_factor_levels 0: ILU(0) in the natural row order, level-scheduled
                            * (monolithic system, or the scalar blocks inside fieldsplit / Picard); single context */
+  PPH_PC_PMG = 6          /* pph_pmg (scalar blocks; inside fieldsplit / Picard, as inner_pc_type): one symmetric V-cycle whose
+                           * top level is the context's own operator and whose lower levels are the CG-1 geometric hierarchy
+                           * on the same cells.  Degree 2: mg_smooth Chebyshev-Jacobi steps on the Q2 / P2 operator, restriction
+                           * to the CG-1 space of the same cells (the degree-2 nodes are the CG-1 nodes of the mesh refined
+                           * once, so this is the h-transfer stencil), the PPH_PC_MG cycle there, and back.  Degree 1: there is
+                           * no p-level to add, PPH_PC_PMG is PPH_PC_MG. */
 };
 
 typedef struct {
@@ -74,7 +80,7 @@ typedef struct {
   /* block solves of the field-split PC / Picard sweeps (fieldsplit_0_/fieldsplit_1_ options;
    * the reference's LU block solves become inner Krylov solves run to inner_rtol)          */
   int32_t inner_ksp_type;   /* PPH_KSP_PREONLY | PPH_KSP_CG | PPH_KSP_GMRES (restart 30, zero guess per solve) */
-  int32_t inner_pc_type;    /* PPH_PC_NONE | PPH_PC_JACOBI | PPH_PC_MG | PPH_PC_ILU */
+  int32_t inner_pc_type;    /* PPH_PC_NONE | PPH_PC_JACOBI | PPH_PC_MG | PPH_PC_ILU | PPH_PC_PMG */
   int32_t inner_max_it;
   int32_t picard;        /* 0: Krylov on the monolithic system; 1: block Picard (fixed-stress)
                           * outer loop per reference src/perphil/forms/dpp.py:196-203       */
@@ -83,7 +89,8 @@ typedef struct {
   double picard_rtol;    /* snes_rtol */
   double picard_atol;    /* snes_atol */
   int32_t picard_max_it; /* snes_max_it */
-  int32_t mg_smooth;     /* smoothing steps per level side for PPH_PC_MG (default 2)     */
+  int32_t mg_smooth;     /* smoothing steps per level side for PPH_PC_MG / PPH_PC_PMG (default 2; every level, the
+                          * degree-2 one included) */
   double inner_reduction; /* > 0: block solves stop once their preconditioned residual has dropped by this
                           * factor from its value at the start of the solve (inexact Picard sweeps; warm
                           * starts make the sequence converge to the exact fixed point), or at inner_rtol,
@@ -133,8 +140,10 @@ int pph_mesh_build(pph_ctx* ctx, int dim, int cell_kind, int nx, int ny, int nz,
 /* Whole mesh (one context, no slabs) with Lagrange pressures of degree 1 or 2 (reference create_function_spaces(mesh,
  * pressure_deg=...), src/perphil/forms/spaces.py:5-36).  Degree 1 is pph_mesh_build of the whole mesh.  Degree 2: Q2 / P2
  * nodes on the refined lattice (numbering above; nodes per cell 9 / 6 / 27 / 10); every call below then works on those
- * nodes, on CSR operators (no stencil-ELL storage, no multigrid hierarchy): a cfg with pc_type mg, or whose field-split /
- * Picard block solves use mg, returns PPH_ERR_INVALID with a message, and so does pph_darcy_velocity*. */
+ * nodes, on CSR operators (no stencil-ELL storage).  Multigrid at degree 2 is PPH_PC_PMG (block solves of a field split /
+ * Picard sweep: the degree-2 operator on top of the CG-1 hierarchy of the same cells).  A cfg with pc_type mg, or whose
+ * field-split / Picard block solves use PPH_PC_MG, returns PPH_ERR_INVALID with a message, and so does
+ * pph_darcy_velocity*. */
 int pph_mesh_build_lagrange(pph_ctx* ctx, int dim, int cell_kind, int nx, int ny, int nz, int degree);
 int pph_mesh_sizes(const pph_ctx* ctx, int64_t* n_nodes, int64_t* n_cells, int32_t* nodes_per_cell,
                    int64_t* nnz_block);
@@ -196,6 +205,17 @@ int pph_get_rhs(pph_ctx* ctx, double* rhs_host /* len 2n */, double* u0_host /* 
 int pph_spmv(pph_ctx* ctx, int which, const double* x_host, double* y_host);
 /* `reps` back-to-back device SpMVs on resident vectors, average kernel ms via HIP events */
 int pph_spmv_bench(pph_ctx* ctx, int which, int reps, double* avg_ms);
+/* z = B r: ONE application of a block preconditioner of the assembled system to a host vector (no reference counterpart:
+ * PETSc's PCApply; here for parity checks of a cycle itself rather than of its fixed point).  which: 0 the A11 block, 1 the
+ * A22 block (length n each).  pc_type: PPH_PC_JACOBI | PPH_PC_MG | PPH_PC_PMG | PPH_PC_ILU; mg_smooth as in pph_solver_cfg
+ * (<= 0: 2).  The entries of r on constrained dofs are taken as 0, as the residuals of the Krylov loops are; the result is 0
+ * there.  PPH_PC_MG on a degree-2 context returns PPH_ERR_INVALID, PPH_PC_PMG on a degree-1 context is PPH_PC_MG.  Single
+ * context only. */
+int pph_pc_apply(pph_ctx* ctx, int which, int pc_type, int mg_smooth, const double* r_host, double* z_host);
+/* diagnostic (tools/pmg_probe.py): `reps` applications to a device-resident vector of ones, timed with HIP events.
+ * out4: ms per application; ms of it in the passes over the degree-2 level (PPH_PC_PMG at degree 2, else 0); bytes those
+ * passes move per application (the kernels of pph_pmg.hip, else 0); ms of set-up the call had to do first */
+int pph_pc_bench(pph_ctx* ctx, int which, int pc_type, int mg_smooth, int reps, double* out4);
 
 /* HBM bandwidth calibration on this device (tools/bw_probe.py, tools/pmc_probe.py): `bytes` streamed with
  * 16 B per lane by `blocks` workgroups, mode 0 read-only, mode 1 copy; average ms per launch. */
@@ -364,6 +384,11 @@ int pph_get_timers(pph_ctx* ctx, double* out, int n);
  *                        below instead of loading them; 0 takes effect at once, 1 at the next assembly
  *   "fold_finals" [1]    single context: the final reductions of p.Ap and of the multigrid cycle's r.z are summed inside the
  *                        kernels that consume them instead of by launches of their own (same sums, same order)
+ *   "pmg_fused" [1]      PPH_PC_PMG at degree 2: the smoother steps and residuals of the degree-2 level run in the tile kernels
+ *                        of pph_pmg.hip (product + Chebyshev recurrence, or product + masked residual, in one pass; lanes
+ *                        dealt over the entries of a tile of rows instead of a fixed count per row); 0: the generic
+ *                        composition CSR product + vector kernels, for comparison from one build.  "pmg_tile_rows" [32]:
+ *                        rows per tile of those kernels on 3D meshes, 32 or 16 (16 measured slower on Q2 64^3)
  *   "transfer_bench"     diagnostic: times `value` launches of the fine-level interpolation / restriction kernels of an existing
  *                        hexahedral hierarchy and prints the result on stderr (tools/r4_transfer_probe.py) */
 int pph_set_option(pph_ctx* ctx, const char* name, double value);

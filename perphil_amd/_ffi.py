@@ -23,7 +23,7 @@ LIB_PATH = os.environ.get("PERPHIL_HIP_LIB") or os.path.join(_HERE, "libperphil_
 PPH_OK, PPH_ERR_INVALID, PPH_ERR_HIP, PPH_ERR_NOMEM, PPH_ERR_DIVERGED, PPH_ERR_COMM = 0, -1, -2, -3, -4, -5
 CELL_QUAD, CELL_TRI, CELL_HEX, CELL_TET = 0, 1, 2, 3
 KSP_PREONLY, KSP_CG, KSP_GMRES = 0, 1, 2
-PC_NONE, PC_JACOBI, PC_BLOCK2, PC_FIELDSPLIT, PC_MG, PC_ILU = 0, 1, 2, 3, 4, 5
+PC_NONE, PC_JACOBI, PC_BLOCK2, PC_FIELDSPLIT, PC_MG, PC_ILU, PC_PMG = 0, 1, 2, 3, 4, 5, 6
 MAT_MONO, MAT_K, MAT_M, MAT_A11, MAT_A22, MAT_A12, MAT_A21 = 0, 1, 2, 3, 4, 5, 6
 
 # every symbol include/perphil_hip.h declares (checked by tests/test_abi.py)
@@ -39,6 +39,7 @@ EXPORTS = [
     "pph_darcy_velocity",
     "pph_get_stream", "pph_copy_solution_device", "pph_set_dirichlet_device", "pph_error_norms_mms_device",
     "pph_error_norms_sampled_device", "pph_darcy_velocity_device",
+    "pph_pc_apply", "pph_pc_bench",
 ]
 
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64)
@@ -176,6 +177,8 @@ def _load() -> C.CDLL:
         "pph_error_norms_sampled_device": ([p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
                                             f64p, f64p], C.c_int),
         "pph_darcy_velocity_device": ([p, C.c_void_p, C.c_double, C.c_void_p], C.c_int),
+        "pph_pc_apply": ([p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
+        "pph_pc_bench": ([p, C.c_int, C.c_int, C.c_int, C.c_int, f64p], C.c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = ABI mismatch: fail loudly
@@ -565,6 +568,23 @@ class Context:
         y = np.empty_like(x)
         self._check(lib.pph_spmv(self._h, which, _ptr(x), _ptr(y)))
         return y
+
+    def pc_apply(self, which: int, pc_type: int, r: np.ndarray, mg_smooth: int = 2) -> np.ndarray:
+        """z = B r: one application of the block preconditioner `pc_type` (PC_JACOBI, PC_MG, PC_PMG, PC_ILU) of block
+        `which` (0: A11, 1: A22) of the assembled system.  Entries of r on constrained dofs count as 0."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        if r.shape != (self.n,):
+            raise ValueError(f"pc_apply: r must have shape ({self.n},)")
+        z = np.empty_like(r)
+        self._check(lib.pph_pc_apply(self._h, int(which), int(pc_type), int(mg_smooth), _ptr(r), _ptr(z)))
+        return z
+
+    def pc_bench(self, which: int, pc_type: int, reps: int, mg_smooth: int = 2) -> dict:
+        """Timing of `reps` applications of a block preconditioner on the device (tools/pmg_probe.py)."""
+        out = np.zeros(4, dtype=np.float64)
+        self._check(lib.pph_pc_bench(self._h, int(which), int(pc_type), int(mg_smooth), int(reps),
+                                     out.ctypes.data_as(C.POINTER(C.c_double))))
+        return {"apply_ms": out[0], "level0_ms": out[1], "level0_bytes": out[2], "setup_ms": out[3]}
 
     def spmv_bench(self, which: int, reps: int) -> float:
         ms = C.c_double()

@@ -191,6 +191,7 @@ int pph_ctx_destroy(pph_ctx* ctx) {
   if (ctx->ev_asm0) (void)hipEventDestroy(ctx->ev_asm0);
   if (ctx->ev_asm1) (void)hipEventDestroy(ctx->ev_asm1);
   if (ctx->ev_lam) (void)hipEventDestroy(ctx->ev_lam);
+  for (hipEvent_t& e : ctx->pmg_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
   if (ctx->h_lam) (void)hipHostFree(ctx->h_lam);
   ctx->mg_lam.release();
   if (ctx->ev_x) (void)hipEventDestroy(ctx->ev_x);
@@ -757,6 +758,12 @@ int pph_set_option(pph_ctx* ctx, const char* name, double value) {
   if (!strcmp(name, "asm_ring")) { ctx->asm_ring = value > 0.0 ? (int)value : 0; return PPH_OK; }
   if (!strcmp(name, "asm_keep_km")) { ctx->asm_keep_km = value != 0.0 ? 1 : 0; return PPH_OK; }
   if (!strcmp(name, "coarse_max_it")) { ctx->coarse_max_it = value >= 1 ? (int)value : 1; return PPH_OK; }
+  if (!strcmp(name, "pmg_tile_rows")) {
+    PPH_REQUIRE(ctx, value == 16.0 || value == 32.0, "pmg_tile_rows: 16 or 32");
+    ctx->pmg_tile_rows = (int)value;
+    return PPH_OK;
+  }
+  if (!strcmp(name, "pmg_fused")) { ctx->pmg_fused = value != 0.0 ? 1 : 0; return PPH_OK; }
   if (!strcmp(name, "mg_fused")) { ctx->mg_fused = value != 0.0 ? 1 : 0; return PPH_OK; }
   if (!strcmp(name, "mg_tail_rows")) { ctx->mg_tail_rows = (int64_t)value; return PPH_OK; }
   if (!strcmp(name, "coarse_on_device")) { ctx->coarse_on_device = value != 0.0 ? 1 : 0; return PPH_OK; }

@@ -429,6 +429,13 @@ struct pph_ctx {
   int device_scalars = 0;               // 1: the device-scalar CG branch also over the callback transport (tests)
   int mg_fused = 1;                     // V(1,1) cycles on stencil-ELL levels: fused smoother / transfer kernels and the
                                         // single-workgroup tail (pph_mg.hip); 0: the general kernel-per-operation cycle
+  int pmg_fused = 1;                    // PPH_PC_PMG: the degree-2 level's smoother / residual passes run in the tile kernels of pph_pmg.hip;
+                                        // 0: the generic composition la_spmv + k_cheb_step / la_spmv_resid (comparison from one build)
+  int pmg_tile_rows = 32;               // rows per tile of those kernels on 3D meshes: 32 or 16 (2D: 64)
+  int64_t n_pmg_pass = 0;               // passes of those kernels over a degree-2 operator and the bytes they moved (pph_pc_bench)
+  double pmg_bytes = 0;
+  bool pmg_time = false;                // pph_pc_bench: time the degree-2 level's share of a cycle (events around its passes)
+  hipEvent_t pmg_ev[4] = {nullptr, nullptr, nullptr, nullptr};
   DevBuf<double> mg_tail_pack[2];       // operators / inverse diagonals / masks of the tail levels, packed per assembly
   int mg_tail_lt[2] = {-1, -1};         // first tail level the pack was built for
   int64_t mg_tail_rows = 5000;          // levels with at most this many rows are handled inside the tail kernel
@@ -647,6 +654,14 @@ bool mg_pre_smoother(pph_ctx* ctx, int which, int nsmooth, const double** dinv, 
                      bool* launch_only);
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// p-multigrid (pph_pmg.hip): the passes over the degree-2 level of a PPH_PC_PMG cycle
+bool pmg_level0_ok(const pph_ctx* ctx, const Csr& A);   // the tile kernels serve this operator (else: the generic composition)
+// t = A d; r -= t; dnew = c1 d + c2 dinv r; x += dnew   (one Chebyshev-Jacobi step; dnew != d)
+void pmg_cheb_step(pph_ctx* ctx, const Csr& A, const double* dinv, const double* d, double* dnew, double* r, double* x,
+                   double c1, double c2);
+// r = b - A x, 0 on the rows where mask is set (mask may be NULL)
+void pmg_resid(pph_ctx* ctx, const Csr& A, const double* x, const double* b, const uint8_t* mask, double* r);
+void pmg_zero_masked(pph_ctx* ctx, double* v, const uint8_t* mask, int64_t n);
 // symmetric storage (diagonal + upper slots); on slabs (sell_sym_slabs) the ghost rows keep their entries towards owned
 // columns so that owned rows find their lower entries (fuse_elim_diag, pph_assemble.hip)
 static inline int pph_sell_sym(const pph_ctx* ctx) { return (ctx->sell_sym && (ctx->world == 1 || ctx->sell_sym_slabs)) ? 1 : 0; }

@@ -441,7 +441,8 @@ static Csr level_csr(const pph_ctx* ctx, const MgLevel& L, int which, bool lowp 
   A.rowptr = L.rowptr; A.col = L.col; A.val = L.val[which]; A.nrows = L.n; A.nnz = L.nnz;
   if (lowp && ctx->mg_fp32 && L.val32[which].p) A.val32 = L.val32[which].p;
   else A.ell = L.ell[which];
-  A.max_row = ctx->mesh.max_row;
+  // (a degree-2 context: the CG-1 levels below the p-level have their own, shorter rows)
+  A.max_row = (ctx->mesh.degree == 2 && &L != ctx->mg.data()) ? L.mesh.max_row : ctx->mesh.max_row;
   A.geom = (ctx->world > 1 && !L.replicated) ? L.geom : nullptr;
   A.lanes = pph_pick_lanes(ctx, A.nnz, A.nrows);
   return A;
@@ -538,7 +539,12 @@ int mg_setup(pph_ctx* ctx) {
   const MeshData& fm = ctx->mesh;
   const bool dist = ctx->world > 1;
   PPH_REQUIRE(ctx, !dist || fm.dim == 3, "slab decomposition needs a 3D mesh");
-  int nlev = 1;
+  // p-multigrid (PPH_PC_PMG on a degree-2 context): level 0 is the context's degree-2 operator, level 1 the CG-1 operator
+  // on the SAME cells (its nodes are every second lattice point of level 0, so the transfer 0 <-> 1 is the h-transfer with
+  // fine = 2 coarse + d), levels 2.. coarsen the cells as the CG-1 hierarchy does
+  const int pl = (fm.degree == 2) ? 1 : 0;
+  PPH_REQUIRE(ctx, !pl || !dist, "degree-2 meshes are single-context meshes (no slab decomposition)");
+  int nlev = 1 + pl;
   {
     int nx = fm.nx, ny = fm.ny, nz = (fm.dim == 3) ? fm.nz : 0;
     while (nx % 2 == 0 && ny % 2 == 0 && (fm.dim == 2 || nz % 2 == 0) && nx / 2 >= 2 && ny / 2 >= 2 &&
@@ -592,7 +598,8 @@ int mg_setup(pph_ctx* ctx) {
       const MgLevel& F = ctx->mg[l - 1];
       MeshData& m = L.mesh;
       m.dim = fm.dim; m.kind = fm.kind;
-      m.nx = fm.nx >> l; m.ny = fm.ny >> l; m.nz = (fm.dim == 3) ? (fm.nz >> l) : 0;
+      const int lc = l - pl;   // cell coarsening of this level
+      m.nx = fm.nx >> lc; m.ny = fm.ny >> lc; m.nz = (fm.dim == 3) ? (fm.nz >> lc) : 0;
       if (fm.dim == 2) { m.z0 = 0; m.nzl = 0; m.glo = m.ghi = 0; }
       else if (L.replicated || !dist) { m.z0 = 0; m.nzl = m.nz; m.glo = m.ghi = 0; }
       else { m.glo = fm.glo; m.ghi = fm.ghi; m.z0 = (c0 >> l) - m.glo; m.nzl = (c1 >> l) - m.z0; }
@@ -751,11 +758,16 @@ int mg_lam_host(pph_ctx* ctx) {
 // `steps` Chebyshev-Jacobi steps on A x = b.  zero_guess: x is overwritten, no initial SpMV.
 static void chebyshev(pph_ctx* ctx, MgLevel& L, int which, const double* b, double* x, int steps, bool zero_guess) {
   const Csr A = level_csr(ctx, L, which, true);
+  // the degree-2 level of a p-multigrid cycle: products + recurrence in the tile kernels of pph_pmg.hip
+  const bool tile = ctx->mesh.degree == 2 && &L == ctx->mg.data() && pmg_level0_ok(ctx, A);
   if (steps == 1 && ctx->world == 1) {
     // one step = a weighted Jacobi sweep: the weight is read from the device array (no host copy of the bound needed)
     double* r1 = L.r.p;
     const double* r01 = b;
-    if (!zero_guess) { la_spmv_resid(ctx, A, x, b, r1); r01 = r1; }
+    if (!zero_guess) {
+      if (tile) pmg_resid(ctx, A, x, b, nullptr, r1); else la_spmv_resid(ctx, A, x, b, r1);
+      r01 = r1;
+    }
     hipLaunchKernelGGL(k_cheb_init, dim3(mg_grid(L.n)), dim3(256), 0, ctx->stream, x, L.d.p, r01, L.dinv[which].p, 0.0,
                        zero_guess ? 1 : 0, 0, L.n, cheb_wp(ctx, (int)(&L - ctx->mg.data()), which));
     return;
@@ -771,16 +783,24 @@ static void chebyshev(pph_ctx* ctx, MgLevel& L, int which, const double* b, doub
   if (zero_guess) {
     if (steps > 1) la_copy(ctx, r, b, L.n);  // the recurrence updates r in place
     else r0 = b;                              // single step: read b directly
+  } else if (tile) {
+    pmg_resid(ctx, A, x, b, nullptr, r);
   } else {
     la_spmv_resid(ctx, A, x, b, r);
   }
   hipLaunchKernelGGL(k_cheb_init, dim3(grid), dim3(256), 0, ctx->stream, x, L.d.p, r0, L.dinv[which].p, 1.0 / theta,
                      zero_guess ? 1 : 0, steps > 1 ? 1 : 0, L.n);
+  double *dcur = L.d.p, *dnext = L.t.p;   // (tile kernels: the new direction goes to the other buffer)
   for (int s = 1; s < steps; ++s) {
-    la_spmv(ctx, A, L.d.p, L.t.p);
     const double rho_new = 1.0 / (2.0 * sigma - rho);
-    hipLaunchKernelGGL(k_cheb_step, dim3(grid), dim3(256), 0, ctx->stream, x, L.d.p, r, L.t.p, L.dinv[which].p,
-                       rho_new * rho, 2.0 * rho_new / delta, L.n);
+    if (tile) {
+      pmg_cheb_step(ctx, A, L.dinv[which].p, dcur, dnext, r, x, rho_new * rho, 2.0 * rho_new / delta);
+      double* sw = dcur; dcur = dnext; dnext = sw;
+    } else {
+      la_spmv(ctx, A, L.d.p, L.t.p);
+      hipLaunchKernelGGL(k_cheb_step, dim3(grid), dim3(256), 0, ctx->stream, x, L.d.p, r, L.t.p, L.dinv[which].p,
+                         rho_new * rho, 2.0 * rho_new / delta, L.n);
+    }
     rho = rho_new;
   }
 }
@@ -1524,6 +1544,10 @@ void mg_vcycle(pph_ctx* ctx, int which, const double* rin, double* zout, int nsm
     chebyshev(ctx, mg[0], which, rin, zout, nsmooth > 2 ? nsmooth : 2, true);
     return;
   }
+  // p-multigrid: level 0 is the degree-2 operator, the CG-1 hierarchy starts at level 1
+  const bool pmg = ctx->mesh.degree == 2;
+  const bool tile0 = pmg && pmg_level0_ok(ctx, level_csr(ctx, mg[0], which, true));
+  const bool timed = pmg && ctx->pmg_time && ctx->pmg_ev[0];
   // downward leg
   for (int l = 0; l < nlev - 1; ++l) {
     MgLevel& L = mg[l];
@@ -1531,8 +1555,13 @@ void mg_vcycle(pph_ctx* ctx, int which, const double* rin, double* zout, int nsm
     const double* b = (l == 0) ? rin : L.b.p;
     double* x = (l == 0) ? zout : L.x.p;
     ctx->comm_suspended = L.replicated;
+    if (l == 0 && timed) (void)hipEventRecord(ctx->pmg_ev[0], ctx->stream);
     chebyshev(ctx, L, which, b, x, nsmooth, true);
+    // (tile kernel: constrained rows are written as 0, what the restriction's own mask test makes of them anyway)
+    if (l == 0 && tile0) pmg_resid(ctx, level_csr(ctx, L, which, true), x, b, L.maskp[which], L.r.p);
+    else
     la_spmv_resid(ctx, level_csr(ctx, L, which, true), x, b, L.r.p);
+    if (l == 0 && timed) (void)hipEventRecord(ctx->pmg_ev[1], ctx->stream);
     if (dist && !L.replicated) (void)la_halo(ctx, *L.geom, L.r.p);  // restriction reads one fine plane beyond the owned ones
     if (ctx->mesh.kind == PPH_CELL_HEX)
       hipLaunchKernelGGL(k_restrict_q1<3>, dim3(mg_grid(C.n)), dim3(256), 0, ctx->stream, C.b.p, L.r.p, C.maskp[which],
@@ -1548,7 +1577,11 @@ void mg_vcycle(pph_ctx* ctx, int which, const double* rin, double* zout, int nsm
     if (dist && C.replicated && !L.replicated) (void)la_allreduce_vec(ctx, C.b.p, C.n);
   }
   // coarsest level: Jacobi-CG to 1e-12 (a handful of unknowns)
-  {
+  if (pmg && nlev == 2) {
+    // cells that cannot be coarsened: the CG-1 part is what the CG-1 cycle is on such a mesh (see nlev == 1 above)
+    MgLevel& C = mg[1];
+    chebyshev(ctx, C, which, C.b.p, C.x.p, nsmooth > 2 ? nsmooth : 2, true);
+  } else {
     MgLevel& C = mg[nlev - 1];
     int its = 0;
     ctx->comm_suspended = C.replicated;
@@ -1579,7 +1612,9 @@ void mg_vcycle(pph_ctx* ctx, int which, const double* rin, double* zout, int nsm
       hipLaunchKernelGGL(k_prolong_add<1>, dim3(mg_grid(L.n)), dim3(256), 0, ctx->stream, x, C.x.p, L.maskp[which], tg);
     else
       hipLaunchKernelGGL(k_prolong_add<2>, dim3(mg_grid(L.n)), dim3(256), 0, ctx->stream, x, C.x.p, L.maskp[which], tg);
+    if (l == 0 && timed) (void)hipEventRecord(ctx->pmg_ev[2], ctx->stream);
     chebyshev(ctx, L, which, b, x, nsmooth, false);
+    if (l == 0 && timed) (void)hipEventRecord(ctx->pmg_ev[3], ctx->stream);
   }
   ctx->comm_suspended = false;
 }

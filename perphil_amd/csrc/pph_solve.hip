@@ -7,6 +7,7 @@
 // convergence test on the preconditioned residual, ||r|| <= max(rtol*||P^-1 b||, atol), restart 30,
 // classical Gram-Schmidt without refinement, zero initial guess for KSP solves.
 #include "pph_internal.h"
+#include <chrono>
 #include <cmath>
 #include <functional>
 
@@ -573,7 +574,8 @@ struct BlockSolver {
         la_extract_diag_inv(ctx, A[0], dinv[0]);
         la_extract_diag_inv(ctx, A[1], dinv[1]);
       }
-    } else if (cfg->inner_pc_type == PPH_PC_MG) {
+    } else if (cfg->inner_pc_type == PPH_PC_MG || cfg->inner_pc_type == PPH_PC_PMG) {
+      // (PPH_PC_PMG reaches this point on degree-2 contexts only: mg_setup puts their operator on top of the CG-1 hierarchy)
       PPH_TRY(mg_setup(ctx));
     } else if (cfg->inner_pc_type == PPH_PC_ILU) {
       // ILU(0) of both diagonal blocks (CSR values needed: the fused assembly keeps stencil-ELL copies only)
@@ -583,7 +585,7 @@ struct BlockSolver {
       for (int f = 0; f < 2; ++f)
         if (!ctx->ilu[1 + f].valid) PPH_TRY(ilu_factor(ctx, ctx->ilu[1 + f], A[f]));
     } else if (cfg->inner_pc_type != PPH_PC_NONE) {
-      pph_set_error(ctx, "inner pc_type %d not supported for block solves (none, jacobi, mg, ilu)", cfg->inner_pc_type);
+      pph_set_error(ctx, "inner pc_type %d not supported for block solves (none, jacobi, mg, pph_pmg, ilu)", cfg->inner_pc_type);
       return PPH_ERR_INVALID;
     }
     return PPH_OK;
@@ -615,7 +617,8 @@ struct BlockSolver {
     PPH_TRY(work(ctx, W_IQ, (size_t)n, &q));
     ApplyFn pc;
     const int ns = cfg->mg_smooth > 0 ? cfg->mg_smooth : 2;
-    if (cfg->inner_pc_type == PPH_PC_MG) pc = [this, which, ns](const double* in, double* o) { mg_vcycle(ctx, which, in, o, ns); };
+    if (cfg->inner_pc_type == PPH_PC_MG || cfg->inner_pc_type == PPH_PC_PMG)
+      pc = [this, which, ns](const double* in, double* o) { mg_vcycle(ctx, which, in, o, ns); };
     if (cfg->inner_pc_type == PPH_PC_ILU)
       pc = [this, which](const double* in, double* o) { if (ilu_apply(ctx, ctx->ilu[1 + which], in, o) < 0) failed = true; };
     KspOut ko;
@@ -687,7 +690,8 @@ static int validate_cfg(pph_ctx* ctx, const pph_solver_cfg* cfg) {
   PPH_REQUIRE(ctx, cfg != nullptr, "solver cfg is NULL");
   PPH_REQUIRE(ctx, cfg->ksp_type >= PPH_KSP_PREONLY && cfg->ksp_type <= PPH_KSP_GMRES, "unknown ksp_type %d",
               cfg->ksp_type);
-  PPH_REQUIRE(ctx, cfg->pc_type >= PPH_PC_NONE && cfg->pc_type <= PPH_PC_ILU, "unknown pc_type %d", cfg->pc_type);
+  PPH_REQUIRE(ctx, cfg->pc_type >= PPH_PC_NONE && cfg->pc_type <= PPH_PC_PMG, "unknown pc_type %d", cfg->pc_type);
+  PPH_REQUIRE(ctx, cfg->pc_type != PPH_PC_PMG, "pc_type pph_pmg applies to the scalar blocks: use it as inner_pc_type");
   // degree 2 has no multigrid hierarchy: pc mg, and block solves on it (which the LU blocks also stand for), are refused
   PPH_REQUIRE(ctx, ctx->mesh.degree == 1 || (cfg->pc_type != PPH_PC_MG &&
                    !((cfg->pc_type == PPH_PC_FIELDSPLIT || cfg->picard) && cfg->inner_pc_type == PPH_PC_MG)),
@@ -717,6 +721,13 @@ int pph_solve_device(pph_ctx* ctx, const pph_solver_cfg* cfg, pph_solve_info* in
   if (!ctx) return PPH_ERR_INVALID;
   PPH_REQUIRE(ctx, ctx->asm_ok, "pph_solve before pph_assemble_dpp");
   PPH_TRY(validate_cfg(ctx, cfg));
+  // a degree-1 context has no p-level to add: there PPH_PC_PMG is PPH_PC_MG, path for path
+  pph_solver_cfg cfg_mg;
+  if (cfg->inner_pc_type == PPH_PC_PMG && ctx->mesh.degree == 1) {
+    cfg_mg = *cfg;
+    cfg_mg.inner_pc_type = PPH_PC_MG;
+    cfg = &cfg_mg;
+  }
   PPH_HIP(ctx, hipSetDevice(ctx->device));
   const int64_t n = ctx->n, N = 2 * n;
   la_reset_spmv_stats(ctx);
@@ -997,5 +1008,108 @@ int pph_solve(pph_ctx* ctx, const pph_solver_cfg* cfg, double* x_host, pph_solve
   int st = pph_solve_device(ctx, cfg, info, hist, hist_cap);
   if (st < 0 && st != PPH_ERR_DIVERGED) return st;
   PPH_TRY(pph_get_solution(ctx, x_host));
+  return st;
+}
+
+// ---- one block preconditioner, applied to a caller's vector (parity checks of the cycle itself) ----------------------
+static int pc_apply_prepare(pph_ctx* ctx, int which, int* pc_type) {
+  PPH_REQUIRE(ctx, ctx->asm_ok, "pph_pc_apply before pph_assemble_dpp");
+  PPH_REQUIRE(ctx, which == 0 || which == 1, "pph_pc_apply: which must be 0 (A11) or 1 (A22)");
+  PPH_REQUIRE(ctx, ctx->world == 1, "pph_pc_apply: single context only");
+  PPH_REQUIRE(ctx, *pc_type == PPH_PC_JACOBI || *pc_type == PPH_PC_MG || *pc_type == PPH_PC_PMG || *pc_type == PPH_PC_ILU,
+              "pph_pc_apply: pc_type %d is no block preconditioner (jacobi, mg, pph_pmg, ilu)", *pc_type);
+  if (*pc_type == PPH_PC_PMG && ctx->mesh.degree == 1) *pc_type = PPH_PC_MG;
+  PPH_REQUIRE(ctx, *pc_type != PPH_PC_MG || ctx->mesh.degree == 1,
+              "degree-2 spaces have no CG-1-only multigrid hierarchy: pc_type mg is not available; use pph_pmg");
+  PPH_HIP(ctx, hipSetDevice(ctx->device));
+  if (*pc_type == PPH_PC_MG || *pc_type == PPH_PC_PMG) PPH_TRY(mg_setup(ctx));
+  else PPH_TRY(pph_ensure_csr_blocks(ctx));
+  return PPH_OK;
+}
+
+static int pc_apply_device(pph_ctx* ctx, int which, int pc_type, int ns, const double* r, double* z, double* dinv_work) {
+  if (pc_type == PPH_PC_JACOBI) {
+    la_extract_diag_inv(ctx, block_csr(ctx, which), dinv_work);
+    la_pointwise_mult(ctx, z, dinv_work, r, ctx->n);
+  } else if (pc_type == PPH_PC_ILU) {
+    const Csr A = block_csr(ctx, which);
+    if (!ctx->ilu[1 + which].valid) PPH_TRY(ilu_factor(ctx, ctx->ilu[1 + which], A));
+    PPH_REQUIRE(ctx, ilu_apply(ctx, ctx->ilu[1 + which], r, z) >= 0, "pph_pc_apply: ILU(0) application failed");
+  } else {
+    mg_vcycle(ctx, which, r, z, ns);
+  }
+  return PPH_OK;
+}
+
+int pph_pc_apply(pph_ctx* ctx, int which, int pc_type, int mg_smooth, const double* r_host, double* z_host) {
+  if (!ctx) return PPH_ERR_INVALID;
+  PPH_REQUIRE(ctx, r_host && z_host, "NULL vector");
+  PPH_TRY(pc_apply_prepare(ctx, which, &pc_type));
+  const int64_t n = ctx->n;
+  DevBuf<double> r, z, w;
+  PPH_TRY(r.alloc(ctx, (size_t)n));
+  PPH_TRY(z.alloc(ctx, (size_t)n));
+  PPH_TRY(w.alloc(ctx, (size_t)n));
+  PPH_HIP(ctx, hipMemcpyAsync(r.p, r_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  pmg_zero_masked(ctx, r.p, ctx->bcmask[which].p, n);   // as the residuals of the Krylov loops: 0 on constrained rows
+  const int st = pc_apply_device(ctx, which, pc_type, mg_smooth > 0 ? mg_smooth : 2, r.p, z.p, w.p);
+  if (st == PPH_OK) {
+    PPH_HIP(ctx, hipMemcpyAsync(z_host, z.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  PPH_HIP(ctx, hipGetLastError());
+  r.release(); z.release(); w.release();
+  return st;
+}
+
+// diagnostic (tools/pmg_probe.py): `reps` applications of the block preconditioner to a vector of ones.
+// out[0] ms per application, out[1] ms of it spent in the passes over the degree-2 level (PPH_PC_PMG on a degree-2 context,
+// else 0), out[2] bytes those passes move per application (tile kernels only, else 0), out[3] ms of the set-up the
+// call had to do (hierarchy / factorisation; 0 when it was up to date)
+int pph_pc_bench(pph_ctx* ctx, int which, int pc_type, int mg_smooth, int reps, double* out4) {
+  if (!ctx) return PPH_ERR_INVALID;
+  PPH_REQUIRE(ctx, out4 && reps >= 1, "pph_pc_bench: needs reps >= 1 and an output array");
+  PPH_HIP(ctx, hipSetDevice(ctx->device));
+  PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const auto t0 = std::chrono::steady_clock::now();
+  PPH_TRY(pc_apply_prepare(ctx, which, &pc_type));
+  const int64_t n = ctx->n;
+  const int ns = mg_smooth > 0 ? mg_smooth : 2;
+  DevBuf<double> r, z, w;
+  PPH_TRY(r.alloc(ctx, (size_t)n));
+  PPH_TRY(z.alloc(ctx, (size_t)n));
+  PPH_TRY(w.alloc(ctx, (size_t)n));
+  la_set(ctx, r.p, 1.0, n);
+  pmg_zero_masked(ctx, r.p, ctx->bcmask[which].p, n);
+  PPH_TRY(pc_apply_device(ctx, which, pc_type, ns, r.p, z.p, w.p));   // warm-up: factorisation, host copies of the bounds
+  PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  out4[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  for (hipEvent_t& e : ctx->pmg_ev)
+    if (!e) PPH_HIP(ctx, hipEventCreate(&e));
+  const bool p2 = pc_type == PPH_PC_PMG;
+  double ms_all = 0.0, ms_top = 0.0;
+  ctx->n_pmg_pass = 0; ctx->pmg_bytes = 0.0;
+  int st = PPH_OK;
+  for (int i = 0; i < reps && st == PPH_OK; ++i) {
+    ctx->pmg_time = p2;
+    (void)hipEventRecord(ctx->ev0, ctx->stream);
+    st = pc_apply_device(ctx, which, pc_type, ns, r.p, z.p, w.p);
+    (void)hipEventRecord(ctx->ev1, ctx->stream);
+    ctx->pmg_time = false;
+    PPH_HIP(ctx, hipEventSynchronize(ctx->ev1));
+    float ms = 0.f;
+    PPH_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    ms_all += ms;
+    if (p2) {
+      PPH_HIP(ctx, hipEventElapsedTime(&ms, ctx->pmg_ev[0], ctx->pmg_ev[1]));
+      ms_top += ms;
+      PPH_HIP(ctx, hipEventElapsedTime(&ms, ctx->pmg_ev[2], ctx->pmg_ev[3]));
+      ms_top += ms;
+    }
+  }
+  out4[0] = ms_all / reps;
+  out4[1] = ms_top / reps;
+  out4[2] = ctx->pmg_bytes / reps;
+  r.release(); z.release(); w.release();
   return st;
 }

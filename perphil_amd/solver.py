@@ -84,9 +84,11 @@ def _inner_cfg(cfg: _ffi.SolverCfg, subs: List[Dict], notes: List[str]) -> None:
         cfg.inner_exact = 1      # (blocks of at most 4096 rows: one on-chip solve per block instead of a host-driven loop)
         notes.append("block LU -> CG + geometric multigrid, rtol 1e-12 (blocks of <= 4096 rows: one on-chip Jacobi-CG solve)")
         return
-    if p not in ("mg", "jacobi", "none", "ilu"):
-        raise NotImplementedError(f"fieldsplit block pc_type {p!r} is not supported (lu, ilu, mg, jacobi, none)")
-    cfg.inner_pc_type = {"mg": _ffi.PC_MG, "jacobi": _ffi.PC_JACOBI, "none": _ffi.PC_NONE, "ilu": _ffi.PC_ILU}[p]
+    if p not in ("mg", "pph_pmg", "jacobi", "none", "ilu"):
+        raise NotImplementedError(f"fieldsplit block pc_type {p!r} is not supported (lu, ilu, mg, pph_pmg, jacobi, none)")
+    # pph_pmg: the space's own operator on top of the CG-1 multigrid hierarchy of the same cells (degree 2; at degree 1 it is mg)
+    cfg.inner_pc_type = {"mg": _ffi.PC_MG, "pph_pmg": _ffi.PC_PMG, "jacobi": _ffi.PC_JACOBI, "none": _ffi.PC_NONE,
+                         "ilu": _ffi.PC_ILU}[p]
     if k == "preonly":
         cfg.inner_ksp_type = _ffi.KSP_PREONLY
     elif k in ("gmres", "fgmres"):
@@ -200,7 +202,8 @@ def _apply_bcs(ctx: _ffi.Context, W, bcs: List[fd.DirichletBC]) -> None:
 
 
 def degree2_unsupported(cfg: _ffi.SolverCfg, info: dict) -> Optional[str]:
-    """Why a translated configuration cannot run on a degree-2 space (no multigrid hierarchy there), or None."""
+    """Why a translated configuration cannot run on a degree-2 space, or None.  Multigrid there is the block pc_type
+    pph_pmg (PC_PMG); mg, and the LU blocks and direct-equivalent solve that stand on it, stay refused."""
     if info.get("direct_equivalent"):
         return "ksp_type preonly + pc_type lu runs as field-split GMRES with multigrid-CG block solves"
     if cfg.pc_type == _ffi.PC_MG:

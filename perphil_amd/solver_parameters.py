@@ -91,3 +91,15 @@ PICARD_JACOBI_SOLVER_PARAMS: dict = {
     "fieldsplit_0": {"ksp_type": "cg", "pc_type": "jacobi", "ksp_rtol": 1e-10},
     "fieldsplit_1": {"ksp_type": "cg", "pc_type": "jacobi", "ksp_rtol": 1e-10},
 }
+# p-multigrid block solves (pc_type pph_pmg): the space's own operator on top of the CG-1 geometric hierarchy of the same
+# cells - the multigrid of degree-2 spaces, where mg is not available; on a degree-1 space pph_pmg is mg
+FIELDSPLIT_PMG_PARAMS: dict = {
+    **GMRES_PARAMS, **_FIELDSPLIT_BASE,
+    "fieldsplit_0": {"ksp_type": "cg", "pc_type": "pph_pmg", "ksp_rtol": 1e-10},
+    "fieldsplit_1": {"ksp_type": "cg", "pc_type": "pph_pmg", "ksp_rtol": 1e-10},
+}
+PICARD_PMG_SOLVER_PARAMS: dict = {
+    **_PICARD_BASE, **_FIELDSPLIT_BASE,
+    "fieldsplit_0": {"ksp_type": "cg", "pc_type": "pph_pmg", "ksp_rtol": 1e-10},
+    "fieldsplit_1": {"ksp_type": "cg", "pc_type": "pph_pmg", "ksp_rtol": 1e-10},
+}
