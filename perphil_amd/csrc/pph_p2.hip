@@ -199,7 +199,9 @@ int pph_p2_mesh(pph_ctx* ctx, MeshData& mesh) {
   PPH_TRY(cnt.alloc(ctx, (size_t)n));
   hipLaunchKernelGGL(k_p2_row_count, dim3(p2_grid(n)), dim3(256), 0, ctx->stream, cnt.p, g, n);
   int64_t nnz = 0;
-  PPH_TRY(pph_scan_counts(ctx, cnt.p, n, mesh.rowptr, &nnz));
+  const int scanned = pph_scan_counts(ctx, cnt.p, n, mesh.rowptr, &nnz);
+  cnt.release();   // (before the size check, so that a refused mesh does not leak it)
+  PPH_TRY(scanned);
   PPH_REQUIRE(ctx, nnz > 0 && nnz < (int64_t)2147483647, "degree-2 scalar block of %lld entries: beyond the int32 positions of "
               "the CSR pattern", (long long)nnz);
   PPH_TRY(mesh.col.alloc(ctx, (size_t)nnz));
@@ -211,7 +213,6 @@ int pph_p2_mesh(pph_ctx* ctx, MeshData& mesh) {
   PPH_HIP(ctx, hipMemcpyAsync(&h, mx.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   PPH_HIP(ctx, hipGetLastError());
-  cnt.release();
   mx.release();
   mesh.max_row = h;
   mesh.nnzb = nnz;
@@ -270,6 +271,15 @@ static void p2_tables_t(std::vector<double>& tab) {
         tab[(size_t)D * D * mm + a * m + b] += w * (N[a] * N[b]);
       }
   }
+  // the exact tables are rationals whose smallest non-zero magnitude is ~1e-3 of the largest of the same table; what the
+  // quadrature leaves of an exact zero (~1e-17) would otherwise reach K / M as an entry of the size of a rounding error
+  // of the whole element matrix, where the exact entry is 0
+  for (int t = 0; t <= D * D; ++t) {
+    double mx = 0.0;
+    for (int k = 0; k < mm; ++k) mx = std::fmax(mx, std::fabs(tab[(size_t)t * mm + k]));
+    for (int k = 0; k < mm; ++k)
+      if (std::fabs(tab[(size_t)t * mm + k]) <= 1e-12 * mx) tab[(size_t)t * mm + k] = 0.0;
+  }
 }
 
 void pph_p2_tables(int kind, std::vector<double>& tab) {
@@ -322,8 +332,7 @@ __device__ __forceinline__ void p2_frame(const double X[D + 1][3], double G[D][D
 }
 
 template <int KIND>
-__global__ __launch_bounds__(256) void k_p2_km(const double* __restrict__ cx, const double* __restrict__ cy,
-                                               const double* __restrict__ cz, const int64_t* __restrict__ rowptr,
+__global__ __launch_bounds__(256) void k_p2_km(double sx, double sy, double sz, const int64_t* __restrict__ rowptr,
                                                const double* __restrict__ tab, P2Geo g, int64_t n, double* __restrict__ K,
                                                double* __restrict__ M) {
   constexpr int D = (KIND == PPH_CELL_QUAD || KIND == PPH_CELL_TRI) ? 2 : 3;
@@ -337,15 +346,17 @@ __global__ __launch_bounds__(256) void k_p2_km(const double* __restrict__ cx, co
     const int64_t base = rowptr[row], len = rowptr[row + 1] - base;
     for (int64_t k = 0; k < len; ++k) { K[base + k] = 0.0; M[base + k] = 0.0; }
     p2_walk(g, I, J, Kk, [&](int64_t, int bx, int by, int bz, int s, int a) {
+      // the frame relative to the box: lattice offsets / lattice points per unit length.  The differences of the cell's
+      // absolute coordinates (k_p2_coords: I / sx) would carry their rounding, ~u |x|, into J = O(h): a relative error
+      // ~u / h that grows with the mesh; these are exact up to one rounding, the same in every box
       double X[D + 1][3];
 #pragma unroll
       for (int r = 0; r <= D; ++r) {
         int o[3];
         p2_local_offset(KIND, s, p2_frame_node(KIND, r), o);
-        const int64_t nd = (2 * bx + o[0]) + (int64_t)g.px * ((2 * by + o[1]) + (int64_t)g.py * (2 * bz + o[2]));
-        X[r][0] = cx[nd];
-        X[r][1] = cy[nd];
-        X[r][2] = (D == 3) ? cz[nd] : 0.0;
+        X[r][0] = (double)o[0] / sx;
+        X[r][1] = (double)o[1] / sy;
+        X[r][2] = (D == 3) ? (double)o[2] / sz : 0.0;
       }
       double G[D][D], adet;
       p2_frame<D>(X, G, &adet);
@@ -355,13 +366,24 @@ __global__ __launch_bounds__(256) void k_p2_km(const double* __restrict__ cx, co
         const int w = (2 * bx + o[0] - I + 2) + 5 * (2 * by + o[1] - J + 2) + 25 * (2 * bz + o[2] - Kk + 2);
         const int64_t pos = base + mk.below(w);
         const int ab = a * m + b;
-        double kv = 0.0;
+        double kv = 0.0, ka = 0.0;
 #pragma unroll
-        for (int i = 0; i < D; ++i) kv += G[i][i] * tab[(i * D + i) * mm + ab];
+        for (int i = 0; i < D; ++i) {
+          const double t = G[i][i] * tab[(i * D + i) * mm + ab];
+          kv += t;
+          ka += fabs(t);
+        }
 #pragma unroll
         for (int i = 0; i < D; ++i)
 #pragma unroll
-          for (int j = i + 1; j < D; ++j) kv += G[i][j] * (tab[(i * D + j) * mm + ab] + tab[(j * D + i) * mm + ab]);
+          for (int j = i + 1; j < D; ++j) {
+            const double t = G[i][j] * (tab[(i * D + j) * mm + ab] + tab[(j * D + i) * mm + ab]);
+            kv += t;
+            ka += fabs(t);
+          }
+        // an entry that cancels to exactly 0 (e.g. right simplices) leaves ~u of its terms: below its own rounding bound
+        // it is 0 (the non-zero entries of these cells are far above it)
+        if (fabs(kv) <= 16.0 * 1.1102230246251565e-16 * ka) kv = 0.0;
         K[pos] += kv;
         M[pos] += adet * Mref[ab];
       }
@@ -381,8 +403,8 @@ int pph_p2_assemble_KM(pph_ctx* ctx, MeshData& mesh) {
   const P2Geo g = p2_geo(mesh);
   const int grid = p2_grid(mesh.n);
 #define PPH_P2_KM(KD)                                                                                                  \
-  hipLaunchKernelGGL(k_p2_km<KD>, dim3(grid), dim3(256), 0, ctx->stream, mesh.cx.p, mesh.cy.p, mesh.cz.p,             \
-                     mesh.rowptr.p, dt.p, g, mesh.n, mesh.K.p, mesh.M.p)
+  hipLaunchKernelGGL(k_p2_km<KD>, dim3(grid), dim3(256), 0, ctx->stream, 2.0 * mesh.nx, 2.0 * mesh.ny,               \
+                     2.0 * (mesh.nz > 0 ? mesh.nz : 1), mesh.rowptr.p, dt.p, g, mesh.n, mesh.K.p, mesh.M.p)
   if (mesh.kind == PPH_CELL_QUAD) PPH_P2_KM(PPH_CELL_QUAD);
   else if (mesh.kind == PPH_CELL_TRI) PPH_P2_KM(PPH_CELL_TRI);
   else if (mesh.kind == PPH_CELL_HEX) PPH_P2_KM(PPH_CELL_HEX);

@@ -134,7 +134,9 @@ def frame_locals(kind):
 
 
 def element_matrices(kind, X):
-    """K_e, M_e of one affine cell with frame vertices X[0..d]."""
+    """K_e, M_e of one affine cell with frame vertices X[0..d].  Entries that vanish in exact arithmetic come out of the
+    quadrature as ~1e-17 of the largest; they are set to 0 (the exact entries are rationals times the geometry: no
+    non-zero one is below 1e-12 of the largest)."""
     d = dim_of(kind)
     J = (np.asarray(X[1:d + 1]) - np.asarray(X[0])).T
     Ji, det = np.linalg.inv(J), abs(np.linalg.det(J))
@@ -145,6 +147,8 @@ def element_matrices(kind, X):
         g = G @ Ji
         K += w * det * g @ g.T
         M += w * det * np.outer(N, N)
+    for A in (K, M):
+        A[np.abs(A) <= 1e-12 * np.abs(A).max()] = 0.0
     return K, M
 
 
