@@ -221,6 +221,14 @@ int pph_pc_bench(pph_ctx* ctx, int which, int pc_type, int mg_smooth, int reps, 
  * 16 B per lane by `blocks` workgroups, mode 0 read-only, mode 1 copy; average ms per launch. */
 int pph_bw_probe(pph_ctx* ctx, int64_t bytes, int mode, int blocks, double* ms_out);
 
+/* diagnostic, host only (no device is touched): the wave map of the node assembly kernel's two launches (option
+ * asm_node_lines) for a box of px x py x pz nodes (dim 2: pz = 1) with `near[row] != 0` on the rows that need the Dirichlet
+ * masks (null: none); align: the option's value (1: the default alignment of a window's first row, or 2, 4 .. 64 rows).
+ * win: first row of every straight-line window of 64 consecutive rows; pairs: the even row of every
+ * aligned row pair of the general launch, padded to a multiple of 32 pairs.  counts[0..1] receive the two lengths; win /
+ * pairs may be null (sizes only), else they hold at least that many entries. */
+int pph_asm_wave_map(int dim, int px, int py, int pz, int align, const uint8_t* near, uint32_t* win, uint32_t* pairs, int64_t* counts);
+
 /* ---- error norms (post-processing) -----------------------------------------------------------------
  * replaces: l2_error() / h1_seminorm_error() (reference src/perphil/utils/postprocessing.py:89-124) for
  * the manufactured pressures of src/perphil/utils/manufactured_solutions.py:39-51 (2D), :87-88 (3D).

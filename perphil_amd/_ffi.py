@@ -39,7 +39,7 @@ EXPORTS = [
     "pph_darcy_velocity",
     "pph_get_stream", "pph_copy_solution_device", "pph_set_dirichlet_device", "pph_error_norms_mms_device",
     "pph_error_norms_sampled_device", "pph_darcy_velocity_device",
-    "pph_pc_apply", "pph_pc_bench",
+    "pph_pc_apply", "pph_pc_bench", "pph_asm_wave_map",
 ]
 
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64)
@@ -179,6 +179,7 @@ def _load() -> C.CDLL:
         "pph_darcy_velocity_device": ([p, C.c_void_p, C.c_double, C.c_void_p], C.c_int),
         "pph_pc_apply": ([p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
         "pph_pc_bench": ([p, C.c_int, C.c_int, C.c_int, C.c_int, f64p], C.c_int),
+        "pph_asm_wave_map": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, i64p], C.c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = ABI mismatch: fail loudly
@@ -671,8 +672,8 @@ class Context:
         return {"halo_ms": t[0], "allreduce_ms": t[1], "halo_timed": int(t[2]), "allreduce_timed": int(t[3])}
 
     def timers(self) -> dict:
-        t = np.zeros(23, dtype=np.float64)
-        self._check(lib.pph_get_timers(self._h, _ptr(t), 23))
+        t = np.zeros(26, dtype=np.float64)
+        self._check(lib.pph_get_timers(self._h, _ptr(t), 26))
         return {"mesh_ms": t[0], "assemble_ms": t[1], "bc_blocks_ms": t[2], "solve_ms": t[3],
                 "spmv_ms": t[4], "spmv_launches": int(t[5]), "spmv_bytes": t[6],
                 "spmv_dot_ms": t[7], "spmv_dot_launches": int(t[8]), "spmv_dot_bytes": t[9],
@@ -681,4 +682,6 @@ class Context:
                 "split_products": int(t[14]), "symmetric_storage": bool(t[15]),
                 "max_split_partials": int(t[16]),
                 "dict_operators": int(t[17]), "dict_classes": int(t[18]), "dict_status": int(t[19]),
-                "dict_build_ms": t[20], "dict_builds": int(t[21]), "dict_zconst": bool(t[22])}
+                "dict_build_ms": t[20], "dict_builds": int(t[21]), "dict_zconst": bool(t[22]),
+                # rows the two launches of the fine level's node assembly stored last (0: one launch), rows of the level
+                "asm_rows_straight": int(t[23]), "asm_rows_general": int(t[24]), "asm_rows": int(t[25])}

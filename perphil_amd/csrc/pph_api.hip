@@ -175,6 +175,7 @@ int pph_ctx_destroy(pph_ctx* ctx) {
   ctx->mesh.release_all();
   for (int f = 0; f < 2; ++f) { ctx->bcmask[f].release(); ctx->g[f].release(); }
   ctx->rownear.release();
+  ctx->wmap.release();
   ctx->sell_tmp.release();
   ctx->post_u.release();
   ctx->bc_bad.release();
@@ -748,6 +749,13 @@ int pph_set_option(pph_ctx* ctx, const char* name, double value) {
   if (!strcmp(name, "asm_node_xmap")) { ctx->asm_node_xmap = value != 0.0 ? 1 : 0; return PPH_OK; }
   if (!strcmp(name, "asm_node")) { ctx->asm_node = value != 0.0 ? 1 : 0; return PPH_OK; }
   if (!strcmp(name, "asm_uniform")) { ctx->asm_uniform = value != 0.0 ? 1 : 0; return PPH_OK; }
+  if (!strcmp(name, "asm_node_lines")) {
+    const int v = (int)value;
+    PPH_REQUIRE(ctx, v == 0 || v == 1 || (v >= 2 && v <= 64 && (v & (v - 1)) == 0), "asm_node_lines: 0, 1 or a window alignment 2, 4 .. 64 (got %d)", v);
+    ctx->asm_node_lines = v;
+    return PPH_OK;
+  }
+  if (!strcmp(name, "asm_poison")) { ctx->asm_poison = value != 0.0 ? 1 : 0; return PPH_OK; }
   if (!strcmp(name, "asm_node_probe")) { ctx->asm_node_probe = (int)value; return PPH_OK; }
   if (!strcmp(name, "asm_node_split_min")) { ctx->asm_node_split_min = (int64_t)value; return PPH_OK; }
   if (!strcmp(name, "asm_tile_xmap")) { ctx->asm_tile_xmap = value != 0.0 ? 1 : 0; return PPH_OK; }
@@ -843,14 +851,15 @@ int pph_get_timers(pph_ctx* ctx, double* out, int n) {
     (void)hipMemcpyAsync(dst, ctx->D11.state.p, sizeof(dst), hipMemcpyDeviceToHost, ctx->stream);
     (void)hipStreamSynchronize(ctx->stream);
   }
-  const double v[23] = {ctx->t_mesh, ctx->t_asm, ctx->t_bc, ctx->t_solve,
+  const double v[26] = {ctx->t_mesh, ctx->t_asm, ctx->t_bc, ctx->t_solve,
                         ctx->t_spmv[0], (double)ctx->n_spmv[0], ctx->spmv_bytes[0],
                         ctx->t_spmv[1], (double)ctx->n_spmv[1], ctx->spmv_bytes[1], (double)ctx->n_halo,
                         ctx->t_spmv_fine, (double)ctx->n_spmv_fine, ctx->spmv_bytes_fine, (double)ctx->n_split,
                         (ctx->ell_ok && ctx->S11.sym) ? 1.0 : 0.0, (double)ctx->max_split_partials,
                         (double)dn, (double)(ctx->D11.tried ? ctx->D11.ncls : 0), (double)(ctx->D11.on ? dst[1] : ctx->D11.status),
-                        ctx->t_dict_build, (double)ctx->n_dict_build, zc11 ? 1.0 : 0.0};
-  for (int i = 0; i < n && i < 23; ++i) out[i] = v[i];
+                        ctx->t_dict_build, (double)ctx->n_dict_build, zc11 ? 1.0 : 0.0,
+                        ctx->asm_rows_win, ctx->asm_rows_gen, ctx->asm_rows_all};
+  for (int i = 0; i < n && i < 26; ++i) out[i] = v[i];
   return PPH_OK;
 }
 

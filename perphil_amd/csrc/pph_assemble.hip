@@ -13,6 +13,7 @@
 // (segments found from the cell->dof map itself, so the merge is also correct on any other numbering).
 #include "pph_internal.h"
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <type_traits>
 
 __device__ inline int64_t find_slot(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
@@ -681,7 +682,13 @@ struct FuseArgs {
   int* dstate[3] = {nullptr, nullptr, nullptr};
   int dn[3] = {0, 0, 0};
   int* alarm = nullptr;
-  // host side only: the group and dictionaries behind the check, and the views they describe
+  // k_asm_node2 in two launches, k_n2_check_general: the wave map that follows the grid lines (WaveMap; n2_wave).  Null: a
+  // wave is 64 consecutive aligned rows
+  const uint32_t* wm_win = nullptr;
+  const uint32_t* wm_pairs = nullptr;
+  int wm_nwin = 0, wm_ngen = 0;
+  // host side only: that map's owner (built on first use); the group and dictionaries behind the check, and the views they describe
+  WaveMap* wm = nullptr;
   DictGroup* G = nullptr;
   SellDict* dicts[3] = {nullptr, nullptr, nullptr};
   const Sell* views[3] = {nullptr, nullptr, nullptr};
@@ -1441,6 +1448,7 @@ static int blocks_prepare(pph_ctx* ctx, bool want_csr) {
     ctx->a21_alias = (h == 0);
     PPH_TRY(ctx->rownear.alloc(ctx, (size_t)n));
     pph_launch_row_near(ctx, ctx->mesh, ctx->bcmask[0].p, ctx->bcmask[1].p, ctx->rownear.p);
+    ctx->wmap.valid = false;
     ctx->bc_dirty = false;
   }
   if (want_csr) { PPH_TRY(pph_ensure_pattern(ctx, ctx->mesh)); PPH_TRY(blocks_alloc_csr(ctx)); }
@@ -2544,6 +2552,148 @@ __device__ __forceinline__ void n2_epilogue(const double (&kv)[DIM == 3 ? 27 : 9
   }
 }
 
+// ---- the wave map: which 64 rows a wave of the node kernel owns, and in which form -----------------------------------
+// ONE definition for the straight-line launch (KIND 1), the general launch (KIND 2), their one-launch form (KIND 0) and
+// k_n2_check_general (KIND 2), so that the launches cannot drift apart: between them they must store every row.
+//
+// Aligned map (fa.wm_win null; KIND 0 always): wave w owns rows [64 w, 64 w + 64) and is straight-line when all of them are
+// `inner` (inside the box, no Dirichlet mask needed).  A line of px nodes is not a multiple of 64, so one wave per line
+// straddles the line's end and takes its interior rows through the general form with it: 26 % of the rows of a 257^3 box,
+// half of those of a 129^3 box, where 5 % and 10 % need that form.
+//
+// Line map (option asm_node_lines, WaveMap, built on the host by n2_wave_map_host from `near` and the box): the straight-line
+// windows are placed INSIDE every maximal run of inner rows (a run never leaves its grid line: the line's end nodes are not
+// inner) - 64 consecutive rows from a multiple of PPH_N2_WIN_ALIGN = 8 rows, every lane inner (the body has no predicate),
+// the last window of a run overlapping its predecessor instead of masking lanes (the overlapped rows are stored twice with the
+// same bits: both forms are one source with pinned roundings).  Every aligned window of the other map lies inside a run
+// and behind its first even row, so a row that was straight-line stays so.  The general launch takes the rows no window
+// covers - and the padding rows up to the next multiple of 64 - as aligned pairs (2 i, 2 i + 1) of adjacent rows, 32 pairs
+// per wave in ascending order; a pair whose other row a window covers stores that row again (same bits).  The spectral
+// bound is a maximum, every other output a plain store of a value that depends on the row only: duplicates are harmless.
+// Alignment (256^3, straight-line launch with the fused check): windows from any even row - all the paired 16-byte stores need -
+// 2.05 ms for 95 % of the rows against 1.01 ms for the aligned map's 74 %: a wave's 512-byte pieces then begin and end inside
+// a 64-byte piece of memory that another wave completes later, and the non-temporal stores leave as partial writes.  From
+// multiples of 8 rows (64 bytes of a slot array) every store instruction writes whole pieces; the general launch's rows are
+// then whole 8-row groups as well.  8 and 16 rows measure the same, 32 and 64 lose rows to the general form for nothing.
+struct N2Wave {
+  uint32_t row;       // the lane's own row: where it stores (a row beyond n: inside the leading dimension, padding)
+  uint32_t node;      // the row its loads use (0 for a lane beyond n; listed mode: the listed node)
+  int gi, gj, gk;
+  bool live, near, fast, run;   // run: this launch has work for the wave (wave-uniform, like fast)
+};
+template <int KIND> __device__ __forceinline__ int n2_wave_count(const FuseArgs& fa, int64_t n) {
+  return (KIND != 0 && fa.wm_win) ? (KIND == 1 ? fa.wm_nwin : fa.wm_ngen) : (int)((n + 63) >> 6);
+}
+template <int DIM, int KIND, bool LISTED>
+__device__ __forceinline__ N2Wave n2_wave(const FuseArgs& fa, int w, int px, int py, int pz, int64_t n) {
+  N2Wave W;
+  const uint32_t lane = threadIdx.x & 63u;
+  const bool lines = KIND != 0 && fa.wm_win != nullptr;
+  if (lines) {
+    // (w is wave-uniform: the window's first row comes through a scalar load)
+    W.row = KIND == 1 ? fa.wm_win[w] + lane : fa.wm_pairs[(uint32_t)w * 32u + (lane >> 1)] + (lane & 1u);
+  } else {
+    W.row = (uint32_t)w * 64u + lane;
+  }
+  W.live = (lines && KIND == 1) || (int64_t)W.row < n;
+  W.node = LISTED ? fa.list[W.row] : (W.live ? W.row : 0u);
+  W.gi = (int)(W.node % (uint32_t)px);
+  const uint32_t tq = W.node / (uint32_t)px;
+  W.gj = (int)(tq % (uint32_t)py);
+  W.gk = (int)(tq / (uint32_t)py);
+  if (lines) {
+    W.near = KIND == 2 && W.live && fa.near[W.node] != 0;
+    W.fast = KIND == 1;
+    W.run = true;
+  } else {
+    W.near = W.live && fa.near[W.node] != 0;
+    const bool inner = W.live && !W.near && W.gi > 0 && W.gi < px - 1 && W.gj > 0 && W.gj < py - 1 && (DIM == 2 || (W.gk > 0 && W.gk < pz - 1));
+    W.fast = __all(inner);
+    W.run = KIND == 0 || (KIND == 1) == W.fast;
+  }
+  return W;
+}
+
+// The line map of a box of px x py x pz nodes (dim 2: pz = 1).  near: one byte per row, or null.  win: first rows of the
+// straight-line windows, ascending; pairs: even rows of the general launch's pairs, ascending, padded with copies of the
+// last one to a multiple of 32; rows[0], rows[1]: distinct rows of the mesh the windows cover / rows the pairs hold.
+static void n2_wave_map_host(int dim, int px, int py, int pz, int align, const uint8_t* near, std::vector<uint32_t>& win,
+                             std::vector<uint32_t>& pairs, int64_t* rows) {
+  if (dim == 2) pz = 1;
+  const int64_t am = ~(int64_t)(align - 1);
+  const int64_t n = (int64_t)px * py * pz, n64 = (n + 63) / 64 * 64;
+  std::vector<uint8_t> cov((size_t)n64, 0);
+  win.clear();
+  pairs.clear();
+  for (int k = (dim == 3 ? 1 : 0); k < (dim == 3 ? pz - 1 : 1); ++k)
+    for (int j = 1; j < py - 1; ++j) {
+      const int64_t line = ((int64_t)k * py + j) * px;
+      int i = 1;
+      while (i < px - 1) {
+        if (near && near[line + i]) { ++i; continue; }
+        const int a = i;
+        while (i < px - 1 && !(near && near[line + i])) ++i;
+        // the run of inner rows [line + a, line + i)
+        const int64_t b = line + i, s = (line + a + align - 1) & am;
+        if (b - s < 64) continue;
+        int64_t w = s;
+        for (; w + 64 <= b; w += 64) win.push_back((uint32_t)w);
+        const int64_t t = (b - 64) & am;                   // the last window: as far up as an aligned first row allows
+        if (t > w - 64) win.push_back((uint32_t)t);
+        for (int64_t r = s; r < t + 64; ++r) cov[(size_t)r] = 1;
+      }
+    }
+  int64_t rw = 0, rg = 0;
+  for (int64_t p = 0; p < n64; p += 2) {
+    rw += cov[(size_t)p] + cov[(size_t)p + 1];
+    if (cov[(size_t)p] && cov[(size_t)p + 1]) continue;
+    pairs.push_back((uint32_t)p);
+    rg += (p < n ? 1 : 0) + (p + 1 < n ? 1 : 0);
+  }
+  while (!pairs.empty() && pairs.size() % 32 != 0) pairs.push_back(pairs.back());
+  if (rows) { rows[0] = rw; rows[1] = rg; }
+}
+
+extern "C" int pph_asm_wave_map(int dim, int px, int py, int pz, int align, const uint8_t* near, uint32_t* win, uint32_t* pairs, int64_t* counts) {
+  if (align == 1) align = PPH_N2_WIN_ALIGN;
+  if (align < 2 || align > 64 || (align & (align - 1)) != 0) return PPH_ERR_INVALID;
+  if ((dim != 2 && dim != 3) || px < 1 || py < 1 || (dim == 3 && pz < 1) || !counts) return PPH_ERR_INVALID;
+  if ((int64_t)px * py * (dim == 3 ? pz : 1) >= ((int64_t)1 << 29)) return PPH_ERR_INVALID;
+  std::vector<uint32_t> w, p;
+  n2_wave_map_host(dim, px, py, pz, align, near, w, p, nullptr);
+  counts[0] = (int64_t)w.size();
+  counts[1] = (int64_t)p.size();
+  if (win) std::copy(w.begin(), w.end(), win);
+  if (pairs) std::copy(p.begin(), p.end(), pairs);
+  return PPH_OK;
+}
+
+// the level's line map on the device: built when `near` changed (the owner clears `valid`) or the box did
+static int n2_wave_map_ensure(pph_ctx* ctx, const MeshData& mesh, const uint8_t* near, WaveMap& W) {
+  const int align = ctx->asm_node_lines == 1 ? PPH_N2_WIN_ALIGN : ctx->asm_node_lines;
+  const int dim = mesh.kind == PPH_CELL_QUAD ? 2 : 3;
+  const int pz = dim == 2 ? 1 : mesh.pzl;
+  if (W.valid && W.n == mesh.n && W.px == mesh.px && W.py == mesh.py && W.pz == pz && W.align == align) return PPH_OK;
+  W.valid = false;
+  std::vector<uint8_t> h((size_t)mesh.n);
+  PPH_HIP(ctx, hipMemcpyAsync(h.data(), near, (size_t)mesh.n, hipMemcpyDeviceToHost, ctx->stream));
+  PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<uint32_t> win, pairs;
+  int64_t rows[2];
+  n2_wave_map_host(dim, mesh.px, mesh.py, pz, align, h.data(), win, pairs, rows);
+  PPH_TRY(W.win.alloc(ctx, win.size()));
+  PPH_TRY(W.pairs.alloc(ctx, pairs.size()));
+  if (!win.empty()) PPH_HIP(ctx, hipMemcpyAsync(W.win.p, win.data(), win.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  if (!pairs.empty()) PPH_HIP(ctx, hipMemcpyAsync(W.pairs.p, pairs.data(), pairs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  W.nwin = (int64_t)win.size();
+  W.ngen = (int64_t)pairs.size() / 32;
+  W.rows_win = rows[0]; W.rows_gen = rows[1];
+  W.n = mesh.n; W.px = mesh.px; W.py = mesh.py; W.pz = pz; W.align = align;
+  W.valid = true;
+  return PPH_OK;
+}
+
 // PATH 0: both bodies in one kernel; 1: only the waves that take the straight-line body, 2: only the others (two
 // launches with separate register allocations; measured against PATH 0)
 template <int DIM, bool SYM, bool SYMC, bool HAS12, bool HAS21, bool HASRHS, bool SAME, int PATH, int MODE = 0, bool UNI = false>
@@ -2572,30 +2722,28 @@ __global__ __launch_bounds__(256, (PATH == 1 && MODE != 1) ? 3 : 2) void k_asm_n
   // fronts), and an XCD-striped order - XCD x takes, plane after plane, the blocks of the x-th in-plane stripe, persistent
   // grid, so that a node's y and z neighbours share an L2 - 3.44 (the general-form waves pile up in the boundary stripes
   // and planes of a static assignment); removed.
-  const int64_t nblk = (n + 255) / 256;
+  // (a block is four consecutive waves of the launch's wave map, n2_wave: consecutive windows, i.e. ascending rows)
+  const int nwv = n2_wave_count<PATH>(fa, n);
+  const int64_t nblk = ((int64_t)nwv + 3) / 4;
   const int64_t bpx = xmap ? (int64_t)(gridDim.x >> 3) : (int64_t)gridDim.x;
   const int64_t cpx = xmap ? (nblk + 7) >> 3 : nblk;
   const int64_t blk0 = xmap ? (int64_t)(blockIdx.x & 7) * cpx : 0;
+  const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   // (A rotated loop - the NEXT block's coordinates requested before this block's stores - was also built and measured: the
   // wait for those loads at the loop head then waits for the stores issued after them as well (one counter, in issue order),
   // and 43 more live registers spill: 1.34 -> 1.91 ms.  The loads stay at the head of their own block.)
   for (int64_t c = xmap ? (blockIdx.x >> 3) : blockIdx.x; c < cpx; c += bpx) {
-    const int64_t node64 = (blk0 + c) * 256 + threadIdx.x;
-    if (node64 - (threadIdx.x & 63) >= n) continue;     // a wave without a row (wave-uniform)
-    // a lane beyond n (last wave only; its index stays inside the leading dimension, a multiple of 64) goes through the general
+    const int64_t wv = (blk0 + c) * 4 + wib;
+    if (wv >= nwv) continue;                            // a wave without a row (wave-uniform)
+    // a lane beyond n (its index stays inside the leading dimension, a multiple of 64) goes through the general
     // form with every predicate 0 and writes the zeros of its padding row: the paired stores need both lanes of a pair
     // (listed mode: n = the rows of the mini operator, a multiple of 64, every one of them a node of the list)
-    const bool live = node64 < n;
-    const uint32_t nodeS = (uint32_t)node64;
-    const uint32_t node = MODE == 2 ? fa.list[nodeS] : (live ? nodeS : 0u);
-    const int gi = (int)(node % (uint32_t)px);
-    const uint32_t tq = node / (uint32_t)px;
-    const int gj = (int)(tq % (uint32_t)py), gk = (int)(tq / (uint32_t)py);
-    const bool near = live && fa.near[node] != 0;
-    const bool inner = live && !near && gi > 0 && gi < px - 1 && gj > 0 && gj < py - 1 && (DIM == 2 || (gk > 0 && gk < pz - 1));
-    const bool fast = __all(inner);
-    const bool do_fast = PATH != 2 && fast, do_gen = PATH != 1 && !fast;
-    if (!do_fast && !do_gen) continue;
+    const N2Wave W = n2_wave<DIM, PATH, MODE == 2>(fa, (int)wv, px, py, pz, n);
+    if (!W.run) continue;
+    const bool live = W.live, near = W.near;
+    const uint32_t nodeS = W.row, node = W.node;
+    const int gi = W.gi, gj = W.gj, gk = W.gk;
+    const bool do_fast = PATH != 2 && W.fast;
     N2Pre<DIM> P;
     n2_fetch<DIM, UNI>(cx, cy, cz, px, py, pz, fa.near, node, gi, gj, gk, 0, P);
     bool has[DIM][2];
@@ -2631,7 +2779,7 @@ __global__ __launch_bounds__(256, (PATH == 1 && MODE != 1) ? 3 : 2) void k_asm_n
 // Fact A of the fused dictionary check for the rows of the GENERAL-form waves: the straight-line launch compares what it
 // stores for free (it waits on memory), the general-form launch has no registers to spare (the compare costs it 1 KB of scratch
 // per lane: 1.0 -> 2.85 ms), so its rows - about a quarter of a uniform box - are read back once: stored half of every
-// operator against the stored half of the row's class, bit for bit.  Same wave classification as k_asm_node2.
+// operator against the stored half of the row's class, bit for bit.  The general launch's waves of the wave map (n2_wave).
 template <int DIM>
 __global__ __launch_bounds__(256) void k_n2_check_general(int px, int py, int pz, int64_t n, FuseArgs fa) {
   constexpr int NSLOT = (DIM == 3) ? 27 : 9, SSC = NSLOT / 2 + 1, C0 = NSLOT / 2;
@@ -2646,18 +2794,15 @@ __global__ __launch_bounds__(256) void k_n2_check_general(int px, int py, int pz
   }
   __syncthreads();
   const double* vals[3] = {fa.A11, fa.A22, fa.A12};
-  const int64_t nblk = (n + 255) / 256;
+  const int nwv = n2_wave_count<2>(fa, n);
+  const int64_t nblk = ((int64_t)nwv + 3) / 4;
+  const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   for (int64_t c = blockIdx.x; c < nblk; c += gridDim.x) {
-    const int64_t node64 = c * 256 + threadIdx.x;
-    if (node64 - (threadIdx.x & 63) >= n) continue;
-    const bool live = node64 < n;
-    const uint32_t node = live ? (uint32_t)node64 : 0u;
-    const int gi = (int)(node % (uint32_t)px);
-    const uint32_t tq = node / (uint32_t)px;
-    const int gj = (int)(tq % (uint32_t)py), gk = (int)(tq / (uint32_t)py);
-    const bool near = live && fa.near[node] != 0;
-    const bool inner = live && !near && gi > 0 && gi < px - 1 && gj > 0 && gj < py - 1 && (DIM == 2 || (gk > 0 && gk < pz - 1));
-    if (__all(inner) || !live) continue;
+    const int64_t wv = c * 4 + wib;
+    if (wv >= nwv) continue;
+    const N2Wave W = n2_wave<DIM, 2, false>(fa, (int)wv, px, py, pz, n);
+    if (!W.run || !W.live) continue;
+    const uint32_t node = W.node;
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
       if (!fa.dtab[d]) continue;
@@ -2845,8 +2990,32 @@ int pph_launch_fused_kernels(pph_ctx* ctx, MeshData& mesh, const FuseArgs& fa, d
         }
         fc.alarm = ctx->dict_alarm_dev;
       }
+      if (ctx->asm_poison) {
+        // test aid: every output row of the level starts as NaNs (all bits set), so that a row no wave stores shows
+        const int ns = mesh.kind == PPH_CELL_QUAD ? 9 : 27;
+        const size_t sd = sym ? ns / 2 + 1 : ns, sc = symc ? ns / 2 + 1 : ns, w = (size_t)mesh.n * 8, pitch = (size_t)fa.ld * 8;
+        PPH_HIP(ctx, hipMemset2DAsync(fa.A11, pitch, 0xFF, w, sd, ctx->stream));
+        PPH_HIP(ctx, hipMemset2DAsync(fa.A22, pitch, 0xFF, w, sd, ctx->stream));
+        if (h12) PPH_HIP(ctx, hipMemset2DAsync(fa.A12, pitch, 0xFF, w, sc, ctx->stream));
+        if (h21) PPH_HIP(ctx, hipMemset2DAsync(fa.A21, pitch, 0xFF, w, sc, ctx->stream));
+        PPH_HIP(ctx, hipMemsetAsync(fa.dinv1, 0xFF, w, ctx->stream));
+        PPH_HIP(ctx, hipMemsetAsync(fa.dinv2, 0xFF, w, ctx->stream));
+        if (hr) { PPH_HIP(ctx, hipMemsetAsync(fa.rhs, 0xFF, 2 * w, ctx->stream)); PPH_HIP(ctx, hipMemsetAsync(fa.u0, 0xFF, 2 * w, ctx->stream)); }
+      }
+      // two launches: the wave map that follows the grid lines (n2_wave; option asm_node_lines), each launch with the
+      // workgroups of its own waves
+      int gridp[3] = {grid, grid, grid};
+      if (split && &mesh == &ctx->mesh) { ctx->asm_rows_all = (double)mesh.n; ctx->asm_rows_win = ctx->asm_rows_gen = 0.0; }
+      if (split && ctx->asm_node_lines && fa.wm) {
+        WaveMap& W = *fa.wm;
+        PPH_TRY(n2_wave_map_ensure(ctx, mesh, fa.near, W));
+        fc.wm_win = W.win.p; fc.wm_pairs = W.pairs.p; fc.wm_nwin = (int)W.nwin; fc.wm_ngen = (int)W.ngen;
+        const int64_t nbw[2] = {((ceil_div64(W.nwin, 4) + 7) / 8) * 8, ((ceil_div64(W.ngen, 4) + 7) / 8) * 8};
+        for (int i = 0; i < 2; ++i) gridp[1 + i] = (int)(nbw[i] < 8 ? 8 : (nbw[i] < 256 * 64 ? nbw[i] : 256 * 64));
+        if (&mesh == &ctx->mesh) { ctx->asm_rows_win = (double)W.rows_win; ctx->asm_rows_gen = (double)W.rows_gen; }
+      }
 #define PPH_N2P(DIMV, S, SC, H12, H21, HR, SM, PATHV, MODEV, UNIV)                                                                      \
-      hipLaunchKernelGGL((k_asm_node2<DIMV, S, SC, H12, H21, HR, SM, PATHV, MODEV, UNIV>), dim3(grid), dim3(256), MODEV == 1 ? lds : 0,    \
+      hipLaunchKernelGGL((k_asm_node2<DIMV, S, SC, H12, H21, HR, SM, PATHV, MODEV, UNIV>), dim3(gridp[PATHV]), dim3(256), MODEV == 1 ? lds : 0,    \
                          ctx->stream, mesh.cx.p, mesh.cy.p, mesh.cz.p, mesh.nx, mesh.ny, nz, mesh.px, mesh.py, pz, mesh.n, fc,           \
                          ctx->asm_node_xmap)
 #define PPH_N2(DIMV, S, SC, H12, H21, HR, SM, UNIV)                                                        \
@@ -2862,7 +3031,7 @@ int pph_launch_fused_kernels(pph_ctx* ctx, MeshData& mesh, const FuseArgs& fa, d
       do {                                                                                                  \
         PPH_N2P(DIMV, S, SC, H12, H21, HR, SM, 1, 1, UNIV);                                                 \
         PPH_N2P(DIMV, S, SC, H12, H21, HR, SM, 2, 0, UNIV);                                                 \
-        hipLaunchKernelGGL(k_n2_check_general<DIMV>, dim3(grid), dim3(256), lds, ctx->stream, mesh.px, mesh.py, pz, mesh.n, fc); \
+        hipLaunchKernelGGL(k_n2_check_general<DIMV>, dim3(gridp[2]), dim3(256), lds, ctx->stream, mesh.px, mesh.py, pz, mesh.n, fc); \
       } while (0)
 #define PPH_N2_DIM(DIMV, UNIV)                                                  \
       switch (variant) {                                                         \
@@ -2960,8 +3129,9 @@ int pph_launch_fused_kernels(pph_ctx* ctx, MeshData& mesh, const FuseArgs& fa, d
 int pph_launch_level_operators(pph_ctx* ctx, MeshData& mesh, const uint8_t* m1, const uint8_t* m2, const uint8_t* near,
                                int same, double coefK1, double coefK2, double coefM, double* A1, double* A2,
                                double* dinv1, double* dinv2, unsigned long long* lam, int64_t ell_ld, int ell_sym,
-                               DictGroup* group, SellDict* dicts, const Sell* views) {
+                               DictGroup* group, SellDict* dicts, const Sell* views, WaveMap* wmap) {
   FuseArgs fa;
+  fa.wm = wmap;
   if (group && dicts && views) {
     fa.G = group;
     for (int d = 0; d < 2; ++d) { fa.dicts[d] = &dicts[d]; fa.views[d] = &views[d]; }
@@ -3017,6 +3187,7 @@ int pph_launch_assemble_fused(pph_ctx* ctx, int monolithic) {
   fa.lam = ctx->lam0.p;
   fa.keep_km = ctx->asm_keep_km;
   fa.same = ctx->a21_alias ? 1 : 0;
+  fa.wm = &ctx->wmap;
   if (ell) {
     fa.G = &ctx->DG;
     fa.dicts[0] = &ctx->D11; fa.dicts[1] = &ctx->D22; fa.dicts[2] = &ctx->D12;

@@ -115,6 +115,22 @@ struct DictGroup {
   const void* cls_of[3] = {nullptr, nullptr, nullptr};
   void release() { list.release(); mini.release(); nlist = 0; nd = 0; ldm = 0; ok = false; }
 };
+// Wave map of the node assembly kernel's two launches (pph_assemble.hip: n2_wave_map_host / n2_wave): which 64 rows a
+// wave owns.  Straight-line windows: 64 consecutive rows, all of them interior and far from constrained dofs, starting at an
+// even row, placed inside the maximal runs of such rows (the last window of a run overlaps its predecessor).  General form:
+// the rows no window covers, as aligned pairs of adjacent rows (2 i, 2 i + 1), 32 pairs per wave.  Depends on the box and
+// the Dirichlet sets only: built once after `rownear`, valid until that changes.
+#define PPH_N2_WIN_ALIGN 8     // rows: a window's first row is a multiple of it (64 bytes of a slot array; measured, pph_assemble.hip "the wave map")
+struct WaveMap {
+  DevBuf<uint32_t> win;              // first row of straight-line window w
+  DevBuf<uint32_t> pairs;            // even row of pair i of the general launch (padded with copies of the last pair to 32 per wave)
+  int64_t nwin = 0, ngen = 0;        // waves of the two launches
+  int64_t rows_win = 0, rows_gen = 0;  // distinct rows of the mesh each launch stores
+  int64_t n = 0;
+  int px = 0, py = 0, pz = 0, align = 0;
+  bool valid = false;
+  void release() { win.release(); pairs.release(); nwin = ngen = rows_win = rows_gen = n = 0; valid = false; }
+};
 struct Sell {
   const double* val = nullptr;
   int64_t ld = 0;            // leading dimension: rows rounded up to a multiple of 64
@@ -248,7 +264,8 @@ struct MgLevel {
   DevBuf<double> dinv[2];
   DevBuf<uint8_t> mask[2];       // per field: non-zero where the dof is constrained
   DevBuf<uint8_t> rownear;       // rows that need the masks (fused level operators); follows the masks
-  DevBuf<uint8_t> rfast[2];      // per field: coarse nodes whose 3^d fine neighbours are all inside, owned and unconstrained (restriction fast path)
+  WaveMap wmap;                  // wave map of the node assembly kernel on this level; follows rownear
+  DevBuf<uint8_t> rfast[2];     // per field: coarse nodes whose 3^d fine neighbours are all inside, owned and unconstrained (restriction fast path)
   int bc_epoch = -1;             // ctx->bc_epoch the masks / rownear were derived from
   const uint8_t* maskp[2] = {nullptr, nullptr};
   DevBuf<double> x, b, r, d, t, w;  // work vectors of the V-cycle (x, b unused on level 0)
@@ -333,6 +350,9 @@ struct pph_ctx {
   int64_t asm_tile_min_nodes = 30000;   // levels with fewer nodes use the two-pass kernels (asm_tile 2: tile kernel always)
   int asm_node_xmap = 0;                // node kernel: blocks dealt round-robin to the XCDs (0, default) or one contiguous eighth per XCD (1: 2.0 instead of 4.1 GB read at 256^3, but 4.5 instead of 3.5 ms)
   int64_t asm_node_split_min = 200000;  // node kernel on levels of at least this many nodes: straight-line waves and the others in two launches
+  int asm_node_lines = 1;               // node kernel in two launches: 1 wave map that follows the grid lines (WaveMap), 0 waves of 64 consecutive aligned rows; 2, 4 .. 64: the line map with windows aligned to that many rows (timing experiments)
+  double asm_rows_win = 0, asm_rows_gen = 0, asm_rows_all = 0;   // rows of the last fine-level node assembly: straight-line launch, general launch, mesh (statistics)
+  int asm_poison = 0;                   // test aid: the node kernel's outputs are filled with NaNs before it runs (a row no wave stores then shows)
   int asm_uniform = 1;                  // node kernel on a uniform box (MeshData::uniform): canonical edges instead of coordinate loads
   int asm_node_probe = 0;               // timing probes (wrong results): 1 skip the straight-line launch, 2 skip the other
   int asm_node = 1;                     // box meshes, stencil-ELL output: one thread per node, registers only (k_asm_node); 0: tile / two-pass kernels
@@ -341,6 +361,7 @@ struct pph_ctx {
   int asm_ring = 0;                     // > 0 (experiment, slower): fused 3D assembly alternates element and node passes over a ring of cell layers, about asm_ring cells per launch
   int asm_keep_km = 0;                  // 1: the fused pass also stores K and M (two more 8 B/nnz streams); 0: they are integrated on demand (pph_get_csr K/M, Darcy projection)
   DevBuf<uint8_t> rownear;              // 1: the row is constrained / ghost or has a constrained column (needs the masks)
+  WaveMap wmap;                         // wave map of the node assembly kernel on the fine level; follows rownear
   bool bc_dirty = true;                 // masks changed since rownear / a21_alias were derived from them
   int bc_epoch = 0;                     // counts changes of the Dirichlet sets (multigrid levels cache injected masks)
   DevBuf<double> g[2];                  // per field Dirichlet values (dense, 0 elsewhere)
@@ -506,7 +527,8 @@ int pph_launch_assemble_fused(pph_ctx* ctx, int monolithic);
 int pph_launch_level_operators(pph_ctx* ctx, MeshData& mesh, const uint8_t* m1, const uint8_t* m2, const uint8_t* near,
                                int same, double coefK1, double coefK2, double coefM, double* A1, double* A2,
                                double* dinv1, double* dinv2, unsigned long long* lam, int64_t ell_ld, int ell_sym,
-                               DictGroup* group = nullptr, SellDict* dicts = nullptr, const Sell* views = nullptr);
+                               DictGroup* group = nullptr, SellDict* dicts = nullptr, const Sell* views = nullptr,
+                               WaveMap* wmap = nullptr);
 void pph_launch_row_near(pph_ctx* ctx, const MeshData& mesh, const uint8_t* m1, const uint8_t* m2, uint8_t* out);   // (stencil walk: no CSR pattern)
 
 // linear algebra on the context stream; all results that feed control flow go through ctx->scal

@@ -491,6 +491,7 @@ void mg_release(pph_ctx* ctx) {
       L.ell[f] = Sell();
     }
     L.x.release(); L.b.release(); L.r.release(); L.d.release(); L.t.release(); L.w.release();
+    L.wmap.release();
   }
   ctx->mg.clear();
   ctx->mg_w.release();
@@ -655,13 +656,15 @@ int mg_setup(pph_ctx* ctx) {
         if (masks_stale) {
           PPH_TRY(L.rownear.alloc(ctx, (size_t)L.n));
           pph_launch_row_near(ctx, m, L.maskp[0], L.maskp[1], L.rownear.p);
+          L.wmap.valid = false;
         }
         for (int f = 0; f < 2; ++f) PPH_TRY(L.dinv[f].alloc(ctx, (size_t)L.n));
         PPH_TRY(pph_launch_level_operators(ctx, m, L.maskp[0], L.maskp[1], L.rownear.p, ctx->a21_alias ? 1 : 0, coefK[0],
                                            coefK[1], ctx->b, ell_only ? L.own_ell[0].p : L.own_val[0].p,
                                            ell_only ? L.own_ell[1].p : L.own_val[1].p, L.dinv[0].p, L.dinv[1].p,
                                            lamdev.p + 2 * l, ell_only ? L.ell[0].ld : 0, ell_only ? L.ell[0].sym : 0,
-                                           ell_only ? &L.dgroup : nullptr, ell_only ? L.dict : nullptr, ell_only ? L.ell : nullptr));
+                                           ell_only ? &L.dgroup : nullptr, ell_only ? L.dict : nullptr, ell_only ? L.ell : nullptr,
+                                           &L.wmap));
         level_fused = true;
         if (ell_only) {
           const int b0 = ctx->n_dict_build;
