@@ -275,6 +275,23 @@ int pph_darcy_velocity(pph_ctx* ctx, const double* p_host, double conductivity, 
  * the last writes to u_dev are enqueued on the context stream */
 int pph_darcy_velocity_device(pph_ctx* ctx, const double* p_dev, double conductivity, double* u_dev);
 
+/* Point evaluation: values and, when grad is not NULL, gradients of a finite-element function at m arbitrary points
+ * replaces: Function.at of Firedrake, which slice_along_x samples (reference src/perphil/utils/postprocessing.py:66-86).
+ * Works on whichever mesh the context holds (CG-1 or degree 2; single context).  nodal: [n][ncomp] (node-major: the CG-1
+ * vector space's layout; a scalar field is ncomp = 1); x: [m][dim]; val: [m][ncomp]; grad: NULL or [m][ncomp][dim].
+ * Location, per direction e: t_e = x_e n_e, box c_e = clamp(floor(t_e), 0, n_e - 1), box-local xi_e = t_e - c_e.  A point
+ * with some xi_e outside [-tol, 1 + tol] (tol >= 0, box-local units; 1e-12 is the Python default) is OUTSIDE: all its outputs
+ * are NaN, and *n_outside receives the number of such points.  Inside points are clamped to [0, 1].  Sub-cells: triangle 0
+ * {0,1,2} where xi_x + xi_y <= 1, else 1 {1,3,2}; the Kuhn tetrahedron whose path 0 -> 7 follows the descending order of
+ * (xi_x, xi_y, xi_z).  Ties: a point on a face shared by sub-cells of a box belongs to the LOWEST sub-cell index, a point on
+ * a face between two boxes to the upper box; values are continuous there, so this shows in gradients only.
+ * The host variant copies everything in and out; the device variant reads and writes caller-owned device arrays on the
+ * context stream and returns after the stream has finished with them (the count is read back). */
+int pph_eval_points(pph_ctx* ctx, const double* nodal_host, int ncomp, const double* x_host, int64_t m, double tol,
+                    double* val_host, double* grad_host, int64_t* n_outside);
+int pph_eval_points_device(pph_ctx* ctx, const double* nodal_dev, int ncomp, const double* x_dev, int64_t m, double tol,
+                           double* val_dev, double* grad_dev, int64_t* n_outside);
+
 /* ---- multi-GPU communication hooks -------------------------------------------------------------
  * replaces: PETSc's implicit VecScatter halo exchange and VecDot all-reduce under mpiexec (never run in
  * the reference).  One context per rank holds one cell slab (pph_mesh_build with

@@ -40,6 +40,7 @@ EXPORTS = [
     "pph_get_stream", "pph_copy_solution_device", "pph_set_dirichlet_device", "pph_error_norms_mms_device",
     "pph_error_norms_sampled_device", "pph_darcy_velocity_device",
     "pph_pc_apply", "pph_pc_bench", "pph_asm_wave_map",
+    "pph_eval_points", "pph_eval_points_device",
 ]
 
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64)
@@ -180,6 +181,9 @@ def _load() -> C.CDLL:
         "pph_pc_apply": ([p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
         "pph_pc_bench": ([p, C.c_int, C.c_int, C.c_int, C.c_int, f64p], C.c_int),
         "pph_asm_wave_map": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, i64p], C.c_int),
+        "pph_eval_points": ([p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, i64p], C.c_int),
+        "pph_eval_points_device": ([p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, i64p],
+                                   C.c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = ABI mismatch: fail loudly
@@ -546,6 +550,24 @@ class Context:
         self.torch_waits()
         return out
 
+    def eval_points_device(self, nodal, points, ncomp: int = 1, gradient: bool = False, tol: float = 1e-12):
+        """eval_points on device tensors: nodal [n * ncomp], points [m, dim] -> (values [m, ncomp], gradients
+        [m, ncomp, dim] or None, number of outside points), tensors on the device.  Nothing but the count moves to the host."""
+        import torch
+
+        nodal = self._device_in(nodal, self.n * int(ncomp), "nodal field")
+        if not (isinstance(points, torch.Tensor) and points.dtype == torch.float64 and points.is_cuda and points.dim() == 2
+                and points.shape[1] == self.dim and points.is_contiguous() and points.device.index == self.device):
+            raise ValueError(f"points must be a contiguous float64 tensor [m, {self.dim}] on cuda:{self.device}")
+        m = points.shape[0]
+        val = self._device_out(m * int(ncomp)).reshape(m, int(ncomp))
+        grad = self._device_out(m * int(ncomp) * self.dim).reshape(m, int(ncomp), self.dim) if gradient else None
+        nout = C.c_int64()
+        self._check(lib.pph_eval_points_device(self._h, _tptr(nodal), int(ncomp), _tptr(points), int(m), float(tol), _tptr(val),
+                                               _tptr(grad) if gradient else None, C.byref(nout)))
+        self.torch_waits()
+        return val, grad, int(nout.value)
+
     # -- export -------------------------------------------------------------------------------
     def csr(self, which: int):
         import scipy.sparse as sp
@@ -601,6 +623,23 @@ class Context:
         self._check(lib.pph_error_norms_mms(self._h, int(field), _ptr(nodal), float(k1), float(k2), float(beta), float(mu),
                                             int(nq), C.byref(l2), C.byref(h1)))
         return l2.value, h1.value
+
+    def eval_points(self, nodal: np.ndarray, points: np.ndarray, ncomp: int = 1, gradient: bool = False, tol: float = 1e-12):
+        """Values of the field nodal [n * ncomp] (node-major) at points [m, dim] (pph_eval_points): (values [m, ncomp],
+        gradients [m, ncomp, dim] or None, number of outside points - whose rows are NaN)."""
+        nodal = np.ascontiguousarray(nodal, dtype=np.float64).reshape(-1)
+        points = np.ascontiguousarray(points, dtype=np.float64)
+        if nodal.shape != (self.n * int(ncomp),):
+            raise ValueError(f"expected {self.n * int(ncomp)} nodal values, got {nodal.shape}")
+        if points.ndim != 2 or points.shape[1] != self.dim:
+            raise ValueError(f"points must have shape [m, {self.dim}], got {points.shape}")
+        m = points.shape[0]
+        val = np.empty((m, int(ncomp)), dtype=np.float64)
+        grad = np.empty((m, int(ncomp), self.dim), dtype=np.float64) if gradient else None
+        nout = C.c_int64()
+        self._check(lib.pph_eval_points(self._h, _ptr(nodal), int(ncomp), _ptr(points), int(m), float(tol), _ptr(val),
+                                        _ptr(grad), C.byref(nout)))
+        return val, grad, int(nout.value)
 
     def quadrature_points(self, nq: int, cell_begin: int, cell_count: int) -> np.ndarray:
         """Physical coordinates [cell_count * nq**dim, dim] of the Gauss points of a cell range (pph_quadrature_points)."""

@@ -587,26 +587,135 @@ class Function:
         self._host()[:] = evaluate(expr, self._space.mesh(), None, getattr(self._space, "degree", 1))
         return self
 
-    def at(self, point: Sequence[float]) -> float:
-        """Value at a point that coincides with a mesh vertex (what ``slice_along_x`` needs); on a degree-2 space at
-        any node of its lattice."""
-        mesh = self._space.mesh()
-        if mesh.distributed:
-            return self.gather().at(point)
-        return float(self._host()[self._vertex(point)])
+    def at(self, arg, dont_raise: bool = False, tolerance: Optional[float] = None):
+        """Value at any point of the domain, or at a batch of points (``fd.Function.at``).
 
-    def _vertex(self, point: Sequence[float]) -> int:
+        ``arg``: one point (a sequence of ``dim`` numbers) or an array / torch tensor of shape ``[m, dim]``.  One point
+        gives a ``float``, a batch an array ``[m]``; on a vector space ``[ncomp]`` / ``[m, ncomp]``; a mixed function gives
+        a tuple with one such entry per sub-function, as in Firedrake.  A single point that coincides with a node of a
+        scalar space (within 1e-9 lattice units) returns that coefficient itself.  Everything else is evaluated on the
+        device (``pph_eval_points``): a device tensor of points gives a device tensor, and a device-resident function is
+        read where it is - host points then cost a copy of the points and of the results only.
+
+        ``tolerance`` (default 1e-12) is in box-local units: a point further outside the unit square / cube raises
+        ``PointNotInDomainError`` naming the first such point - for host points before any GPU work - unless
+        ``dont_raise``: its values are then NaN.  On a distributed mesh the function is gathered first (collective)."""
+        return self._evaluate(arg, False, dont_raise, tolerance)
+
+    def gradient_at(self, arg, dont_raise: bool = False, tolerance: Optional[float] = None):
+        """Gradient of the function at a point or a batch of points, with the rules of ``at``: ``[dim]`` / ``[m, dim]`` on a
+        scalar space, ``[ncomp, dim]`` / ``[m, ncomp, dim]`` on a vector space, a tuple on a mixed function.  The gradient is
+        that of the cell the point is located in (on a face shared by cells: the upper box, then the lowest sub-cell index).
+        Firedrake has no counterpart of this method: there one evaluates ``grad(u)`` through an interpolation or
+        projection first; here ``-k * p.gradient_at(X)`` is the Darcy flux of a pressure of any degree at any point."""
+        return self._evaluate(arg, True, dont_raise, tolerance)
+
+    def _evaluate(self, arg, gradient: bool, dont_raise: bool, tolerance: Optional[float]):
+        mesh = self._space.mesh()
+        dim = mesh.dim
+        tol = 1e-12 if tolerance is None else float(tolerance)
+        if not 0.0 <= tol < 0.5:
+            raise ValueError("tolerance must be in [0, 0.5) box-local units")
+        mixed = isinstance(self._space, MixedFunctionSpace)
+        dev_points = _is_tensor(arg) and arg.is_cuda
+        if dev_points:
+            pts, single = arg, False
+            if pts.dim() != 2 or pts.shape[1] != dim:
+                raise ValueError(f"points must have shape [m, {dim}], got {tuple(pts.shape)}")
+        else:
+            pts = np.asarray(arg.detach().numpy() if _is_tensor(arg) else arg, dtype=np.float64)
+            single = pts.ndim == 1
+            if (single and pts.shape != (dim,)) or (not single and (pts.ndim != 2 or pts.shape[1] != dim)):
+                raise ValueError(f"expected one point of {dim} coordinates or an array [m, {dim}], got shape {pts.shape}")
+            if single and not gradient and not mixed and not isinstance(self._space, VectorFunctionSpace):
+                v = self._vertex(pts)
+                if v is not None:      # a node of the space: the coefficient itself
+                    f = self.gather() if mesh.distributed else self
+                    return float(f._host()[v])
+            pts = np.ascontiguousarray(pts.reshape(-1, dim))
+            outside = _outside_unit_box(pts, (mesh.nx, mesh.ny, mesh.nz)[:dim], tol)
+            if outside.any() and not dont_raise:
+                k = int(np.argmax(outside))
+                raise PointNotInDomainError(f"point {tuple(float(c) for c in pts[k])} (index {k}) is outside the unit "
+                                            f"{'square' if dim == 2 else 'cube'} by more than the tolerance {tol:g}")
+        if mesh.distributed:
+            return self.gather()._evaluate(arg, gradient, dont_raise, tolerance)
+        parts = self.subfunctions if mixed else (self,)
+        if not dev_points and outside.all():      # (nothing to evaluate: no context, no device call)
+            res = [np.full(f._result_shape(pts.shape[0], gradient), np.nan) for f in parts]
+        else:
+            res = [f._evaluate_field(pts, gradient, tol, dont_raise) for f in parts]
+        if single:
+            res = [float(r[0]) if r.ndim == 1 else r[0] for r in res]
+        return tuple(res) if mixed else res[0]
+
+    def _result_shape(self, m: int, gradient: bool):
+        dim = self._space.mesh().dim
+        nc = (getattr(self._space, "value_size", None),) if isinstance(self._space, VectorFunctionSpace) else ()
+        return (m,) + nc + ((dim,) if gradient else ())
+
+    def _evaluate_field(self, pts, gradient: bool, tol: float, dont_raise: bool):
+        """One (vector or scalar) field at host points (ndarray, checked) or device points (tensor)."""
+        V = self._space
+        mesh = V.mesh()
+        deg = getattr(V, "degree", 1)
+        ctx = mesh.context() if deg == 1 else mesh.context(degree=deg)
+        ncomp = V.value_size if isinstance(V, VectorFunctionSpace) else 1
+        dev_points = _is_tensor(pts)
+        if dev_points or self.on_device:
+            import torch
+
+            t = self.torch()
+            u = t if t.is_cuda else t.to(ctx.torch_device())
+            x = pts if dev_points else torch.from_numpy(pts).to(ctx.torch_device())
+            val, grad, nout = ctx.eval_points_device(u.contiguous(), x.contiguous(), ncomp, gradient, tol)
+            if nout and not dont_raise:     # (device points: only the kernel knows; the same rule names the first one)
+                k = int(torch.nonzero(_outside_unit_box_device(x, (mesh.nx, mesh.ny, mesh.nz)[:mesh.dim], tol))[0])
+                raise PointNotInDomainError(f"point {tuple(x[k].tolist())} (index {k}) is outside the unit "
+                                            f"{'square' if mesh.dim == 2 else 'cube'} by more than the tolerance {tol:g}")
+            out = (grad if gradient else val).reshape(self._result_shape(x.shape[0], gradient))
+            return out if dev_points else out.cpu().numpy()
+        val, grad, _ = ctx.eval_points(self._host(), pts, ncomp, gradient, tol)
+        return (grad if gradient else val).reshape(self._result_shape(pts.shape[0], gradient))
+
+    def _vertex(self, point: Sequence[float]) -> Optional[int]:
+        """Index of the node of the space `point` coincides with (within 1e-9 lattice units), or None."""
         mesh = self._space.mesh()
         deg = getattr(self._space, "degree", 1)
-        dims = (deg * mesh.nx, deg * mesh.ny, deg * mesh.nz)[: mesh.dim]
         idx = []
-        for c, nc in zip(point, dims):
+        for c, nc in zip(point, (deg * mesh.nx, deg * mesh.ny, deg * mesh.nz)[: mesh.dim]):
             t = c * nc
-            if abs(t - round(t)) > 1e-9:
-                raise NotImplementedError("Function.at is available at the nodes of the space only")
+            if not (abs(t - round(t)) <= 1e-9 and 0 <= round(t) <= nc):
+                return None
             idx.append(int(round(t)))
         px, py, _ = mesh.lattice_dims(deg)
         return idx[0] + px * (idx[1] + (py * idx[2] if mesh.dim == 3 else 0))
+
+
+class PointNotInDomainError(Exception):
+    """A point given to ``Function.at`` / ``gradient_at`` lies outside the mesh (Firedrake's exception of this name)."""
+
+
+def _outside_unit_box(pts: np.ndarray, boxes: Sequence[int], tol: float) -> np.ndarray:
+    """[m] bool: the point is outside by the evaluation kernel's own rule (pph_eval.hip), in the same arithmetic: per
+    direction t = x n, c = clamp(floor(t), 0, n - 1), xi = t - c outside [-tol, 1 + tol] (NaN: outside)."""
+    n = np.asarray(boxes, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        t = pts * n
+        c = np.clip(np.nan_to_num(np.floor(t), nan=0.0), 0.0, n - 1.0)
+        xi = t - c
+        return ~np.all((xi >= -tol) & (xi <= 1.0 + tol), axis=1)
+
+
+def _outside_unit_box_device(x, boxes: Sequence[int], tol: float):
+    """_outside_unit_box on a device tensor of points (fp64 multiply, floor and subtraction round as the kernel's do)."""
+    import torch
+
+    n = torch.tensor(boxes, dtype=torch.float64, device=x.device)
+    t = x * n
+    c = torch.minimum(torch.clamp(torch.nan_to_num(torch.floor(t), nan=0.0), min=0.0), n - 1.0)
+    xi = t - c
+    return ~torch.all((xi >= -tol) & (xi <= 1.0 + tol), dim=1)
 
 
 Expr = Union[float, Constant, np.ndarray, Callable[[np.ndarray], np.ndarray], Function]

@@ -64,11 +64,17 @@ def calculate_darcy_velocity_from_pressure(pressure_field: fd.Function, conducti
 
 
 def slice_along_x(scalar_field: fd.Function, x_value: float) -> Tuple[np.ndarray, np.ndarray]:
-    """(y_points, values) of a scalar field along the vertical line x = x_value (a grid line)."""
+    """(y_points, values) of a scalar field along the vertical line x = x_value, any x_value in [0, 1], at the ny + 1 grid
+    heights.  On a grid line (every sample a node of the space) the values are the coefficients themselves; otherwise one
+    batched point evaluation on the device (``Function.at``)."""
     mesh = scalar_field.function_space().mesh()
     if mesh.dim != 2:
         raise NotImplementedError("slice_along_x is a 2D utility (as in the reference)")
     y_points = np.arange(mesh.ny + 1) / mesh.ny
+    if scalar_field._vertex((x_value, 0.0)) is None:
+        # between grid lines: one batch (a device-resident field is read where it is)
+        X = np.stack([np.full(mesh.ny + 1, float(x_value)), y_points], axis=1)
+        return y_points, np.asarray(scalar_field.at(X))
     if scalar_field.on_device:
         # only the slice's values travel: gathered on the device, then copied
         import torch
