@@ -113,7 +113,9 @@ typedef struct {
   int32_t inner_iterations;  /* total inner Krylov iterations                            */
   int32_t converged;         /* 1 / 0                                                    */
   int32_t inner_failed;      /* 1: a block solve of the field-split PC / a Picard sweep, or the coarsest multigrid
-                              * solve, hit its iteration limit or broke down (the outer result may still converge) */
+                              * solve, hit its iteration limit or broke down (the outer result may still converge);
+                              * also an on-chip LU-equivalent block solve that ended short of its tolerance
+                              * (pph_get_timers out[26..28]) */
   double resnorm;            /* final (preconditioned) residual norm (ksp.getResidualNorm(), solver.py:74) */
   double rhs_norm;           /* ||F(u0)||_2, PETSc's "0 SNES Function norm"               */
 } pph_solve_info;
@@ -351,7 +353,14 @@ int pph_comm_times(pph_ctx* ctx, double* out4);
  * out[20] ms spent so far in FIRST builds of row dictionaries (hash build + table + first bitwise check + the read-back of
  * the verdict; once per operator, mesh and Dirichlet-set pair - a symbolic-phase cost like the pattern of a CSR matrix),
  * out[21] how many such builds; out[22] 1 when the products of A11 take the classes of the interior planes from the plane below
- * (option "sell_dict_zconst": the class words of four planes only are read - launches count (16 + e) nrows bytes + those). */
+ * (option "sell_dict_zconst": the class words of four planes only are read - launches count (16 + e) nrows bytes + those);
+ * out[23] / out[24] rows the two launches of the fine level's node assembly stored last (straight-line windows / general form;
+ * 0: one launch), out[25] rows of that level;
+ * out[26] on-chip LU-equivalent block solves of the last solve (cfg.inner_exact on a single context, blocks of at most 4096 rows
+ * in stencil-ELL storage: one workgroup runs the whole Jacobi-CG of a block solve, the host does not wait for it), out[27] how
+ * many of them ended WITHOUT meeting their tolerance (iteration limit, option "onchip_max_it", or p.Ap <= 0; a zero right-hand
+ * side counts as converged) - any such solve sets pph_solve_info.inner_failed = 1 and converged = 0: it is reported, not
+ * repeated on the host-driven loop - out[28] their CG iterations summed.  All three are 0 when the path did not run. */
 int pph_get_timers(pph_ctx* ctx, double* out, int n);
 /* tuning / profiling switches (no reference counterpart; defaults in brackets):
  *   "op_format" [1]      operator format of the scalar blocks inside block solves / Picard sweeps: 1 stencil-ELL
@@ -378,6 +387,8 @@ int pph_get_timers(pph_ctx* ctx, double* out, int n);
  *   "mg_fused" [1]       V(1,1) on stencil-ELL levels: fused smoother / transfer kernels + on-chip tail; 0 general cycle
  *   "mg_tail_rows" [5000] levels with at most min(this, 1024) rows join the single-workgroup tail of the cycle
  *   "coarse_max_it" [500] iteration limit of the coarsest-level Jacobi-CG (reported through inner_failed)
+ *   "onchip_max_it" [0]  iteration limit of an on-chip LU-equivalent block solve (rtol 1e-12); 0: 8 n + 64 for n rows.  A solve
+ *                        that stops there is reported through inner_failed and pph_get_timers out[27]
  *   "mg_fp32" [0], "mg_replicate_below" [40000 nodes], "coarse_on_device" [1]   multigrid: fp32 copies of the V-cycle
  *                        operators (CSR only), replication threshold of coarse levels on slabs, coarsest solve on the device
  *   "mg_replicate_rows_per_rank" [40000], "mg_replicate_cap" [1e6]   slabs: a level is also replicated when its share per

@@ -428,6 +428,7 @@ class Context:
             st = lib.pph_solve(self._h, C.byref(cfg), _ptr(x), C.byref(info), _ptr(hist), int(hist_cap))
         else:
             st = lib.pph_solve_device(self._h, C.byref(cfg), C.byref(info), _ptr(hist), int(hist_cap))
+        self.last_info = info        # (what the solve reported, also when the status below raises)
         self._check(st, allow_diverged=not raise_on_diverged)
         nh = min(hist_cap, info.iterations + 1)
         return x, info, hist[:nh].copy()
@@ -711,8 +712,8 @@ class Context:
         return {"halo_ms": t[0], "allreduce_ms": t[1], "halo_timed": int(t[2]), "allreduce_timed": int(t[3])}
 
     def timers(self) -> dict:
-        t = np.zeros(26, dtype=np.float64)
-        self._check(lib.pph_get_timers(self._h, _ptr(t), 26))
+        t = np.zeros(29, dtype=np.float64)
+        self._check(lib.pph_get_timers(self._h, _ptr(t), 29))
         return {"mesh_ms": t[0], "assemble_ms": t[1], "bc_blocks_ms": t[2], "solve_ms": t[3],
                 "spmv_ms": t[4], "spmv_launches": int(t[5]), "spmv_bytes": t[6],
                 "spmv_dot_ms": t[7], "spmv_dot_launches": int(t[8]), "spmv_dot_bytes": t[9],
@@ -723,4 +724,7 @@ class Context:
                 "dict_operators": int(t[17]), "dict_classes": int(t[18]), "dict_status": int(t[19]),
                 "dict_build_ms": t[20], "dict_builds": int(t[21]), "dict_zconst": bool(t[22]),
                 # rows the two launches of the fine level's node assembly stored last (0: one launch), rows of the level
-                "asm_rows_straight": int(t[23]), "asm_rows_general": int(t[24]), "asm_rows": int(t[25])}
+                "asm_rows_straight": int(t[23]), "asm_rows_general": int(t[24]), "asm_rows": int(t[25]),
+                # on-chip LU-equivalent block solves of the last solve: how many ran, how many ended short of their tolerance
+                # (iteration limit or p.Ap <= 0; any of them sets SolveInfo.inner_failed), their CG iterations summed
+                "onchip_solves": int(t[26]), "onchip_unconverged": int(t[27]), "onchip_cg_iterations": int(t[28])}

@@ -141,6 +141,12 @@ int pph_ctx_create(int device, pph_ctx** out) {
     delete ctx;
     return PPH_ERR_NOMEM;
   }
+  ctx->h_onchip = reinterpret_cast<unsigned long long*>(ctx->h_scal + PPH_MAX_SCAL + 5);   // (spare words 5..7 of the mirror)
+  if (ctx->onchip_rec.alloc(ctx, 4) < 0 || hipMemset(ctx->onchip_rec.p, 0, 4 * sizeof(unsigned long long)) != hipSuccess) {
+    g_last_error = ctx->err;
+    delete ctx;
+    return PPH_ERR_NOMEM;
+  }
   *out = ctx;
   return PPH_OK;
 }
@@ -185,6 +191,7 @@ int pph_ctx_destroy(pph_ctx* ctx) {
   for (auto& p : ctx->ev_pool) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
   ctx->scal.release();
   ctx->pub_ctr.release();
+  ctx->onchip_rec.release();
   la_release_graphs(ctx);
   if (ctx->h_scal) (void)hipHostFree(ctx->h_scal);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -766,6 +773,7 @@ int pph_set_option(pph_ctx* ctx, const char* name, double value) {
   if (!strcmp(name, "asm_ring")) { ctx->asm_ring = value > 0.0 ? (int)value : 0; return PPH_OK; }
   if (!strcmp(name, "asm_keep_km")) { ctx->asm_keep_km = value != 0.0 ? 1 : 0; return PPH_OK; }
   if (!strcmp(name, "coarse_max_it")) { ctx->coarse_max_it = value >= 1 ? (int)value : 1; return PPH_OK; }
+  if (!strcmp(name, "onchip_max_it")) { ctx->onchip_max_it = value >= 1 ? (int)value : 0; return PPH_OK; }
   if (!strcmp(name, "pmg_tile_rows")) {
     PPH_REQUIRE(ctx, value == 16.0 || value == 32.0, "pmg_tile_rows: 16 or 32");
     ctx->pmg_tile_rows = (int)value;
@@ -851,15 +859,16 @@ int pph_get_timers(pph_ctx* ctx, double* out, int n) {
     (void)hipMemcpyAsync(dst, ctx->D11.state.p, sizeof(dst), hipMemcpyDeviceToHost, ctx->stream);
     (void)hipStreamSynchronize(ctx->stream);
   }
-  const double v[26] = {ctx->t_mesh, ctx->t_asm, ctx->t_bc, ctx->t_solve,
+  const double v[29] = {ctx->t_mesh, ctx->t_asm, ctx->t_bc, ctx->t_solve,
                         ctx->t_spmv[0], (double)ctx->n_spmv[0], ctx->spmv_bytes[0],
                         ctx->t_spmv[1], (double)ctx->n_spmv[1], ctx->spmv_bytes[1], (double)ctx->n_halo,
                         ctx->t_spmv_fine, (double)ctx->n_spmv_fine, ctx->spmv_bytes_fine, (double)ctx->n_split,
                         (ctx->ell_ok && ctx->S11.sym) ? 1.0 : 0.0, (double)ctx->max_split_partials,
                         (double)dn, (double)(ctx->D11.tried ? ctx->D11.ncls : 0), (double)(ctx->D11.on ? dst[1] : ctx->D11.status),
                         ctx->t_dict_build, (double)ctx->n_dict_build, zc11 ? 1.0 : 0.0,
-                        ctx->asm_rows_win, ctx->asm_rows_gen, ctx->asm_rows_all};
-  for (int i = 0; i < n && i < 26; ++i) out[i] = v[i];
+                        ctx->asm_rows_win, ctx->asm_rows_gen, ctx->asm_rows_all,
+                        (double)ctx->onchip_solves, (double)ctx->onchip_unconverged, (double)ctx->onchip_its};
+  for (int i = 0; i < n && i < 29; ++i) out[i] = v[i];
   return PPH_OK;
 }
 

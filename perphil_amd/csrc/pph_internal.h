@@ -462,6 +462,13 @@ struct pph_ctx {
   int64_t mg_tail_rows = 5000;          // levels with at most this many rows are handled inside the tail kernel
   int coarse_max_it = 500;              // iteration limit of the coarsest-level Jacobi-CG (to rtol 1e-12)
   int coarse_failed = 0;                // host-driven coarsest solves of the last solve that stopped at their iteration limit
+  // on-chip LU-equivalent block solves (BlockSolver::solve -> mg_onchip_cg): the kernel adds to a three-word record on the
+  // device {solves, solves that ended short of their tolerance, CG iterations}; a solve that used the path copies it into the
+  // spare words behind the host mirror with its last launches and reads it after its final synchronisation
+  DevBuf<unsigned long long> onchip_rec;
+  unsigned long long* h_onchip = nullptr;
+  int64_t onchip_solves = 0, onchip_unconverged = 0, onchip_its = 0;   // of the last solve (pph_get_timers out[26..28])
+  int onchip_max_it = 0;                // iteration limit of an on-chip block solve; 0: 8 n + 64
   int coarse_on_device = 1;             // coarsest multigrid level (<= 4096 rows): CG inside one workgroup, no host round trips
   int spmv_bench_mode = 0;              // pph_spmv_bench protocol: 0 back-to-back, 1-3 interleaved (see pph_api.hip)
   int64_t mg_replicate_below = 40000;   // slabs: multigrid levels with at most this many global nodes are replicated
@@ -668,7 +675,7 @@ int mg_transfer_bench(pph_ctx* ctx, int which, int reps, double* out2);   // dia
 // Jacobi-CG of a stencil-ELL operator of at most 4096 rows inside ONE workgroup (the coarsest multigrid level's kernel;
 // also the reference's LU blocks on plumbing-size meshes): x = A^-1 b to rtol, zero guess; r, p, q: work vectors of n
 void mg_onchip_cg(pph_ctx* ctx, const Sell& E, const double* dinv, const double* b, double* x, double* r, double* p, double* q,
-                  int64_t n, double rtol, int max_it);
+                  int64_t n, double rtol, int max_it, unsigned long long* rec);
 void mg_release(pph_ctx* ctx);
 // z = Vcycle(r) for block `which` (0: A11, 1: A22); r and z have fine-level length n
 void mg_vcycle(pph_ctx* ctx, int which, const double* r, double* z, int nsmooth);

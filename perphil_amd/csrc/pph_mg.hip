@@ -822,11 +822,23 @@ __device__ __forceinline__ double coarse_block_sum(double v, double* lds) {
   return t;
 }
 
+// How a solve ended, for the host to read when the enclosing pph_solve* ends (no round trip per solve): rec[0] solves,
+// rec[1] solves that ended short of tol (iteration limit, or p.Ap <= 0 / NaN), rec[2] iterations (updates of x).  Launches
+// on one stream follow each other, so one lane adds with plain loads and stores.  rec == nullptr: nothing is recorded
+// (the coarsest-level solves of the V-cycle).
+__device__ __forceinline__ void coarse_record(unsigned long long* rec, bool converged, int its) {
+  if (rec != nullptr && threadIdx.x == 0) {
+    rec[0] += 1ull;
+    rec[1] += converged ? 0ull : 1ull;
+    rec[2] += (unsigned long long)its;
+  }
+}
+
 __global__ __launch_bounds__(1024) void k_coarse_cg(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                     const double* __restrict__ val, const double* __restrict__ dinv,
                                                     const double* __restrict__ b, double* __restrict__ x,
                                                     double* __restrict__ r, double* __restrict__ p, double* __restrict__ q,
-                                                    int n, double rtol, int max_it) {
+                                                    int n, double rtol, int max_it, unsigned long long* rec) {
   __shared__ double lds[16];
   const int tid = threadIdx.x, nt = blockDim.x;
   double zz = 0.0, rz = 0.0;
@@ -838,7 +850,7 @@ __global__ __launch_bounds__(1024) void k_coarse_cg(const int64_t* __restrict__ 
   zz = coarse_block_sum(zz, lds);
   rz = coarse_block_sum(rz, lds);
   const double tol = rtol * sqrt(zz);
-  if (!(sqrt(zz) > tol)) return;         // zero (or NaN) right-hand side: x = 0
+  if (!(sqrt(zz) > tol)) { coarse_record(rec, zz == 0.0, 0); return; }   // zero right-hand side: x = 0, converged (NaN: not)
   for (int it = 0; it < max_it; ++it) {
     __syncthreads();                     // p complete
     double pq = 0.0;
@@ -849,7 +861,7 @@ __global__ __launch_bounds__(1024) void k_coarse_cg(const int64_t* __restrict__ 
       pq += p[i] * s;
     }
     pq = coarse_block_sum(pq, lds);
-    if (!(pq > 0.0)) return;
+    if (!(pq > 0.0)) { coarse_record(rec, false, it); return; }
     const double alpha = rz / pq;
     double zz2 = 0.0, rz2 = 0.0;
     for (int i = tid; i < n; i += nt) {
@@ -860,12 +872,13 @@ __global__ __launch_bounds__(1024) void k_coarse_cg(const int64_t* __restrict__ 
     }
     zz2 = coarse_block_sum(zz2, lds);
     rz2 = coarse_block_sum(rz2, lds);
-    if (sqrt(zz2) <= tol) return;
+    if (sqrt(zz2) <= tol) { coarse_record(rec, true, it + 1); return; }
     const double beta = rz2 / rz;
     __syncthreads();                     // every thread has read p[col] of this iteration's product
     for (int i = tid; i < n; i += nt) p[i] = dinv[i] * r[i] + beta * p[i];
     rz = rz2;
   }
+  coarse_record(rec, false, max_it);
 }
 
 // the same solve on a stencil-ELL operator (no CSR values exist on a level the fused pass wrote in that form)
@@ -873,7 +886,8 @@ __global__ __launch_bounds__(1024) void k_coarse_cg_sell(const double* __restric
                                                          int px, int py, int pz, const double* __restrict__ dinv,
                                                          const double* __restrict__ b, double* __restrict__ x,
                                                          double* __restrict__ r, double* __restrict__ p,
-                                                         double* __restrict__ q, int n, double rtol, int max_it) {
+                                                         double* __restrict__ q, int n, double rtol, int max_it,
+                                                         unsigned long long* rec) {
   __shared__ double lds[16];
   const int tid = threadIdx.x, nt = blockDim.x;
   double zz = 0.0, rz = 0.0;
@@ -885,7 +899,7 @@ __global__ __launch_bounds__(1024) void k_coarse_cg_sell(const double* __restric
   zz = coarse_block_sum(zz, lds);
   rz = coarse_block_sum(rz, lds);
   const double tol = rtol * sqrt(zz);
-  if (!(sqrt(zz) > tol)) return;
+  if (!(sqrt(zz) > tol)) { coarse_record(rec, zz == 0.0, 0); return; }
   for (int it = 0; it < max_it; ++it) {
     __syncthreads();
     double pq = 0.0;
@@ -907,7 +921,7 @@ __global__ __launch_bounds__(1024) void k_coarse_cg_sell(const double* __restric
       pq += p[i] * s;
     }
     pq = coarse_block_sum(pq, lds);
-    if (!(pq > 0.0)) return;
+    if (!(pq > 0.0)) { coarse_record(rec, false, it); return; }
     const double alpha = rz / pq;
     double zz2 = 0.0, rz2 = 0.0;
     for (int i = tid; i < n; i += nt) {
@@ -918,18 +932,19 @@ __global__ __launch_bounds__(1024) void k_coarse_cg_sell(const double* __restric
     }
     zz2 = coarse_block_sum(zz2, lds);
     rz2 = coarse_block_sum(rz2, lds);
-    if (sqrt(zz2) <= tol) return;
+    if (sqrt(zz2) <= tol) { coarse_record(rec, true, it + 1); return; }
     const double beta = rz2 / rz;
     __syncthreads();
     for (int i = tid; i < n; i += nt) p[i] = dinv[i] * r[i] + beta * p[i];
     rz = rz2;
   }
+  coarse_record(rec, false, max_it);
 }
 
 void mg_onchip_cg(pph_ctx* ctx, const Sell& E, const double* dinv, const double* b, double* x, double* r, double* p, double* q,
-                  int64_t n, double rtol, int max_it) {
+                  int64_t n, double rtol, int max_it, unsigned long long* rec) {
   hipLaunchKernelGGL(k_coarse_cg_sell, dim3(1), dim3(n <= 256 ? 256 : 1024), 0, ctx->stream, E.val, E.ld, E.sym, make_stencil(E.kind),
-                     E.px, E.py, E.pz, dinv, b, x, r, p, q, (int)n, rtol, max_it);
+                     E.px, E.py, E.pz, dinv, b, x, r, p, q, (int)n, rtol, max_it, rec);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1489,7 +1504,7 @@ static void mg_vcycle_fused(pph_ctx* ctx, int which, const double* rin, double* 
     if ((!dist || C.replicated) && C.n <= 4096 && ctx->coarse_on_device)
       hipLaunchKernelGGL(k_coarse_cg_sell, dim3(1), dim3(C.n <= 256 ? 256 : 1024), 0, ctx->stream, C.ell[which].val,
                          C.ell[which].ld, C.ell[which].sym, make_stencil(kind), C.px, C.py, C.pz, C.dinv[which].p, C.b.p, C.x.p, C.r.p,
-                         C.d.p, C.t.p, (int)C.n, 1e-12, ctx->coarse_max_it);
+                         C.d.p, C.t.p, (int)C.n, 1e-12, ctx->coarse_max_it, (unsigned long long*)nullptr);
     else
       pph_cg_jacobi(ctx, level_csr(ctx, C, which), C.b.p, C.x.p, C.dinv[which].p, 1e-12, 0.0, ctx->coarse_max_it, C.r.p, C.d.p, C.t.p,
                     C.w.p, &its);
@@ -1591,10 +1606,10 @@ void mg_vcycle(pph_ctx* ctx, int which, const double* rin, double* zout, int nsm
     if ((!dist || C.replicated) && C.n <= 4096 && ctx->coarse_on_device && C.ell[which].val)
       hipLaunchKernelGGL(k_coarse_cg_sell, dim3(1), dim3(C.n <= 256 ? 256 : 1024), 0, ctx->stream, C.ell[which].val,
                          C.ell[which].ld, C.ell[which].sym, make_stencil(ctx->mesh.kind), C.px, C.py, C.pz, C.dinv[which].p, C.b.p, C.x.p,
-                         C.r.p, C.d.p, C.t.p, (int)C.n, 1e-12, ctx->coarse_max_it);
+                         C.r.p, C.d.p, C.t.p, (int)C.n, 1e-12, ctx->coarse_max_it, (unsigned long long*)nullptr);
     else if ((!dist || C.replicated) && C.n <= 4096 && ctx->coarse_on_device)
       hipLaunchKernelGGL(k_coarse_cg, dim3(1), dim3(C.n <= 256 ? 256 : 1024), 0, ctx->stream, C.rowptr, C.col, C.val[which],
-                         C.dinv[which].p, C.b.p, C.x.p, C.r.p, C.d.p, C.t.p, (int)C.n, 1e-12, ctx->coarse_max_it);
+                         C.dinv[which].p, C.b.p, C.x.p, C.r.p, C.d.p, C.t.p, (int)C.n, 1e-12, ctx->coarse_max_it, (unsigned long long*)nullptr);
     else
       pph_cg_jacobi(ctx, level_csr(ctx, C, which), C.b.p, C.x.p, C.dinv[which].p, 1e-12, 0.0, ctx->coarse_max_it, C.r.p, C.d.p, C.t.p,
                     C.w.p, &its);

@@ -555,6 +555,7 @@ struct BlockSolver {
   double* dinv[2] = {nullptr, nullptr};
   int total_its = 0;
   bool failed = false;
+  bool onchip_used = false;              // an on-chip block solve ran: its record is read when the solve ends
   double bnorm_cache[2] = {-1.0, -1.0};  // ||P^-1 b|| of the first (cold) solve of each block
   double* last_resid = nullptr;          // recurrence residual rhs - A z of the last CG solve (work vector)
 
@@ -626,8 +627,15 @@ struct BlockSolver {
       // the reference's LU block on a plumbing-size mesh (16 x 16: 289 rows): the whole block solve inside one workgroup,
       // Jacobi-CG to inner_rtol on chip - one launch instead of ~9 host-driven multigrid-CG iterations of ~10 launches and
       // one round trip each (BASELINE config 1 through solve_dpp: 20 -> ~2 ms)
+      // How each of these solves ended is not looked at here (that would be the round trip this path exists to avoid): the
+      // kernel adds to ctx->onchip_rec, which pph_solve_device reads once, after its final synchronisation.  A solve that
+      // stops short is REPORTED (inner_failed), not repeated on the host-driven loop.
+      if (!onchip_used) {
+        PPH_HIP(ctx, hipMemsetAsync(ctx->onchip_rec.p, 0, 3 * sizeof(unsigned long long), ctx->stream));
+        onchip_used = true;
+      }
       mg_onchip_cg(ctx, A[which].ell, ctx->dinv0[which].p, rhs, z, r, p, q, n, cfg->inner_rtol < 1e-12 ? cfg->inner_rtol : 1e-12,
-                   8 * (int)n + 64);
+                   ctx->onchip_max_it > 0 ? ctx->onchip_max_it : 8 * (int)n + 64, ctx->onchip_rec.p);
       last_resid = nullptr;
       total_its += 1;
       return PPH_OK;
@@ -740,6 +748,7 @@ int pph_solve_device(pph_ctx* ctx, const pph_solver_cfg* cfg, pph_solve_info* in
   pph_solve_info inf;
   inf.iterations = 0; inf.inner_iterations = 0; inf.converged = 0; inf.inner_failed = 0; inf.resnorm = 0; inf.rhs_norm = 0;
   ctx->coarse_failed = 0;
+  ctx->onchip_solves = ctx->onchip_unconverged = ctx->onchip_its = 0;
   la_dot(ctx, ctx->rhs.p, ctx->rhs.p, N, S_A);
   PPH_TRY(la_fetch(ctx, S_A, 1));
   inf.rhs_norm = std::sqrt(ctx->h_scal[S_A]);
@@ -962,8 +971,17 @@ int pph_solve_device(pph_ctx* ctx, const pph_solver_cfg* cfg, pph_solve_info* in
     int grid = (int)(ceil_div64(N, 256) < 2048 ? ceil_div64(N, 256) : 2048);
     hipLaunchKernelGGL(k_add2, dim3(grid), dim3(256), 0, ctx->stream, ctx->sol.p, ctx->u0.p, du, N);
   }
+  // the record of the on-chip block solves travels with the solve's last launches (pinned destination: no wait of its own)
+  if (bs.onchip_used)
+    PPH_HIP(ctx, hipMemcpyAsync(ctx->h_onchip, ctx->onchip_rec.p, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
   PPH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   PPH_HIP(ctx, hipEventSynchronize(ctx->ev1));
+  if (bs.onchip_used) {
+    ctx->onchip_solves = (int64_t)ctx->h_onchip[0];
+    ctx->onchip_unconverged = (int64_t)ctx->h_onchip[1];
+    ctx->onchip_its = (int64_t)ctx->h_onchip[2];
+    if (ctx->onchip_unconverged > 0) { inf.inner_failed = 1; inf.converged = 0; }   // as bs.failed: the preconditioner was not the one asked for
+  }
   float ms = 0.f;
   PPH_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
   ctx->t_solve = ms;
