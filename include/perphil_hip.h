@@ -294,6 +294,35 @@ int pph_eval_points(pph_ctx* ctx, const double* nodal_host, int ncomp, const dou
 int pph_eval_points_device(pph_ctx* ctx, const double* nodal_dev, int ncomp, const double* x_dev, int64_t m, double tol,
                            double* val_dev, double* grad_dev, int64_t* n_outside);
 
+/* ---- mass balance (post-processing; perphil_amd/csrc/pph_flux.hip) --------------------------------------------
+ * No reference counterpart: the reference stops at pressures and a projected velocity.  These stand beside
+ * calculate_darcy_velocity_from_pressure() (reference src/perphil/utils/postprocessing.py:34-63: the same flux
+ * -conductivity grad p_h, integrated here instead of projected) and the model's mass transfer xi = beta/mu (p1 - p2)
+ * (reference src/perphil/forms/dpp.py:27).  They work on whichever mesh the context holds (CG-1 or degree 2, all four cell
+ * kinds), need neither Dirichlet data nor an assembled system, and require a single context (a mesh, world == 1:
+ * PPH_ERR_INVALID with a message otherwise).  fp64, no floating-point atomics: two calls give the same bits.  The host
+ * variants upload their field and run the device variant; the device variants read caller-owned device arrays on the context
+ * stream and return after the stream has finished with them. */
+/* out[0] = int p_h dx over the unit square / cube (postprocessing.py:34-63 integrates nothing; dpp.py:27 is the integrand of the
+ * transfer T = beta/mu (int p1 - int p2)); nodal: n values; exact for the finite-element function */
+int pph_integrate(pph_ctx* ctx, const double* nodal_host, double* out /* [1], host */);
+int pph_integrate_device(pph_ctx* ctx, const double* nodal_dev, double* out /* [1], host */);
+/* out[s - 1] = F_s = int_{side s} -conductivity grad p_h . n ds (the integrand of postprocessing.py:34-63 on the boundary), sides
+ * numbered as Firedrake numbers UnitSquareMesh / UnitCubeMesh: 1: x = 0, 2: x = 1, 3: y = 0, 4: y = 1, 5: z = 0, 6: z = 1; n the
+ * outward axis direction, the gradient that of the cell that owns the facet (a cell on an edge or corner of the domain counts for
+ * every side it touches); exact for the finite-element function.  Entries past 2 dim are set to 0.  The work is proportional to
+ * the boundary cell layers, not to the mesh. */
+int pph_boundary_flux(pph_ctx* ctx, const double* nodal_host, double conductivity, double* out /* [6], host */);
+int pph_boundary_flux_device(pph_ctx* ctx, const double* nodal_dev, double conductivity, double* out /* [6], host */);
+/* Consistent nodal fluxes: the residual of the UN-ELIMINATED operator of dpp.py:27,57,89 on any mixed field p = (p1, p2),
+ *   r1 = (k1/mu) K p1 + (beta/mu) M (p1 - p2),   r2 = (k2/mu) K p2 - (beta/mu) M (p1 - p2),
+ * K and M the stiffness and mass matrices without Dirichlet rows (pph_get_csr which = 1, 2; integrated on demand and kept by
+ * the mesh, like pph_darcy_velocity's of postprocessing.py:34-63).  p, r: 2n values, field-major like the solution.  r_f[i] is
+ * minus the outward flux of network f weighted with phi_i: 1^T r1 = T = -1^T r2 with T = beta/mu (int p1 - int p2) for any
+ * field, and at a converged solution the entries on free nodes are the solver's residual. */
+int pph_dpp_nodal_flux(pph_ctx* ctx, double k1, double k2, double beta, double mu, const double* p_host, double* r_host);
+int pph_dpp_nodal_flux_device(pph_ctx* ctx, double k1, double k2, double beta, double mu, const double* p_dev, double* r_dev);
+
 /* ---- multi-GPU communication hooks -------------------------------------------------------------
  * replaces: PETSc's implicit VecScatter halo exchange and VecDot all-reduce under mpiexec (never run in
  * the reference).  One context per rank holds one cell slab (pph_mesh_build with

@@ -41,6 +41,8 @@ EXPORTS = [
     "pph_error_norms_sampled_device", "pph_darcy_velocity_device",
     "pph_pc_apply", "pph_pc_bench", "pph_asm_wave_map",
     "pph_eval_points", "pph_eval_points_device",
+    "pph_integrate", "pph_integrate_device", "pph_boundary_flux", "pph_boundary_flux_device",
+    "pph_dpp_nodal_flux", "pph_dpp_nodal_flux_device",
 ]
 
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64)
@@ -184,6 +186,12 @@ def _load() -> C.CDLL:
         "pph_eval_points": ([p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, i64p], C.c_int),
         "pph_eval_points_device": ([p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, i64p],
                                    C.c_int),
+        "pph_integrate": ([p, C.c_void_p, f64p], C.c_int),
+        "pph_integrate_device": ([p, C.c_void_p, f64p], C.c_int),
+        "pph_boundary_flux": ([p, C.c_void_p, C.c_double, f64p], C.c_int),
+        "pph_boundary_flux_device": ([p, C.c_void_p, C.c_double, f64p], C.c_int),
+        "pph_dpp_nodal_flux": ([p] + [C.c_double] * 4 + [C.c_void_p, C.c_void_p], C.c_int),
+        "pph_dpp_nodal_flux_device": ([p] + [C.c_double] * 4 + [C.c_void_p, C.c_void_p], C.c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = ABI mismatch: fail loudly
@@ -568,6 +576,44 @@ class Context:
                                                _tptr(grad) if gradient else None, C.byref(nout)))
         self.torch_waits()
         return val, grad, int(nout.value)
+
+    # -- mass balance (pph_flux.hip): a NumPy array is uploaded for the call, a device tensor is read where it is ----
+    def _nodal_arg(self, nodal, n: int, name: str):
+        if isinstance(nodal, np.ndarray):
+            a = np.ascontiguousarray(nodal, dtype=np.float64)
+            if a.shape != (n,):
+                raise ValueError(f"{name} must have {n} values, got {a.shape}")
+            return a, _ptr(a), False
+        return nodal, _tptr(self._device_in(nodal, n, name)), True
+
+    def integrate(self, nodal) -> float:
+        """int p_h dx of a nodal field of the context's space (pph_integrate / pph_integrate_device)."""
+        keep, ptr, dev = self._nodal_arg(nodal, self.n, "nodal field")
+        out = C.c_double()
+        fn = lib.pph_integrate_device if dev else lib.pph_integrate
+        self._check(fn(self._h, ptr, C.byref(out)))
+        return out.value
+
+    def boundary_flux(self, nodal, conductivity: float) -> np.ndarray:
+        """F_s = int_{side s} -conductivity grad p_h . n ds, s = 1 .. 2 dim, as an array [2 dim] (pph_boundary_flux)."""
+        keep, ptr, dev = self._nodal_arg(nodal, self.n, "nodal field")
+        out = (C.c_double * 6)()
+        fn = lib.pph_boundary_flux_device if dev else lib.pph_boundary_flux
+        self._check(fn(self._h, ptr, float(conductivity), out))
+        return np.array(out[:2 * self.dim], dtype=np.float64)
+
+    def dpp_nodal_flux(self, p, k1: float, k2: float, beta: float, mu: float):
+        """(r1, r2) = residual of the un-eliminated DPP operator on the mixed field p (2n values, field-major): an array
+        for an array, a new device tensor for a device tensor (pph_dpp_nodal_flux / pph_dpp_nodal_flux_device)."""
+        keep, ptr, dev = self._nodal_arg(p, 2 * self.n, "mixed field")
+        if dev:
+            r = self._device_out(2 * self.n)
+            self._check(lib.pph_dpp_nodal_flux_device(self._h, float(k1), float(k2), float(beta), float(mu), ptr, _tptr(r)))
+            self.torch_waits()
+            return r
+        r = np.empty(2 * self.n, dtype=np.float64)
+        self._check(lib.pph_dpp_nodal_flux(self._h, float(k1), float(k2), float(beta), float(mu), ptr, _ptr(r)))
+        return r
 
     # -- export -------------------------------------------------------------------------------
     def csr(self, which: int):

@@ -1,14 +1,16 @@
 """
 Post-processing — mirror of reference ``src/perphil/utils/postprocessing.py``:
 ``split_dpp_solution`` (:6-31), ``calculate_darcy_velocity_from_pressure`` (:34-63), ``slice_along_x`` (:66-86), ``l2_error`` (:89-105), ``h1_seminorm_error``
-(:108-124).  The two error norms run on the device: a Gauss rule per cell on the isoparametric map, with the
+(:108-124); and, without a reference counterpart, the mass balance of a solution: ``integrate``, ``boundary_fluxes``,
+``mass_transfer_rate``, ``consistent_fluxes``, ``mass_balance`` (``pph_flux.hip``).  The two error norms run on the device: a Gauss rule per cell on the isoparametric map, with the
 manufactured pressure evaluated in closed form at every quadrature point (``pph_error_norms_mms``) or, for any other
 exact field, with samples the caller's callable provides at those points (``pph_quadrature_points`` /
 ``pph_error_norms_sampled``).
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from dataclasses import dataclass
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 
@@ -176,3 +178,117 @@ def l2_error(numerical: fd.Function, exact_expr, quadrature_points: int = 6) -> 
 def h1_seminorm_error(numerical: fd.Function, exact_expr, quadrature_points: int = 6) -> float:
     """|numerical - exact|_{H1} (reference postprocessing.py:108-124)."""
     return float(_norms(numerical, exact_expr, quadrature_points)[1])
+
+
+# -- mass balance ------------------------------------------------------------------------------------------------------
+# Sign conventions.  Sides are numbered as Firedrake numbers UnitSquareMesh / UnitCubeMesh (1: x = 0, 2: x = 1, 3: y = 0,
+# 4: y = 1, 5: z = 0, 6: z = 1); a boundary flux is positive OUT of the domain; the transfer T is positive from network 1
+# to network 2; a consistent nodal flux r_f[i] is MINUS the outward flux of network f weighted with phi_i.  Every check of
+# the arguments comes before the first use of a context: a refusal never touches a GPU.
+
+def _scalar_space(field: fd.Function, what: str):
+    V = field.function_space()
+    if isinstance(V, (fd.MixedFunctionSpace, fd.VectorFunctionSpace)):
+        raise ValueError(f"{what} needs a Function on a scalar CG space, got one on a {type(V).__name__}")
+    return V
+
+
+def _mixed_pair(solution: fd.Function):
+    """The two pressure spaces of a mixed solution: ValueError unless it lives on a 2-field mixed space whose fields share
+    one mesh and one degree (the two fields are then vectors over the same nodes of one context)."""
+    W = solution.function_space()
+    if not isinstance(W, fd.MixedFunctionSpace) or W.num_sub_spaces() != 2:
+        raise ValueError(f"Expected a Function on a 2-field MixedFunctionSpace, got one on a {type(W).__name__}")
+    V1, V2 = W.sub(0), W.sub(1)
+    if V1.mesh() is not V2.mesh() or V1.degree != V2.degree:
+        raise ValueError("both pressures must live on the same mesh, in spaces of the same degree")
+    return V1, V2
+
+
+def _serial(f: fd.Function) -> fd.Function:
+    """`f` itself, or on a distributed mesh the whole function on the mesh's serial twin (collective), as ``at`` does."""
+    return f.gather() if f.function_space().mesh().distributed else f
+
+
+def _coefficients(f: fd.Function):
+    """What the context methods take: the device tensor of a device-resident function (read where it is), else the host
+    array (uploaded for the call)."""
+    return f.torch() if f.on_device else f.vector()
+
+
+def integrate(field: fd.Function) -> float:
+    """``int field dx`` over the unit square / cube, exact for the finite-element function (``pph_integrate``)."""
+    _scalar_space(field, "integrate")
+    field = _serial(field)
+    return float(_context(field).integrate(_coefficients(field)))
+
+
+def boundary_fluxes(pressure_field: fd.Function, conductivity) -> Dict[int, float]:
+    """``{s: int_{side s} -conductivity grad(p_h) . n ds}`` for the sides ``s = 1 .. 2 dim``, outward normal, gradient of
+    the cell that owns the facet (``pph_boundary_flux``; the work grows with the boundary, not with the mesh).  For network
+    ``f`` of a DPP solution the conductivity is ``k_f / mu``."""
+    _scalar_space(pressure_field, "boundary_fluxes")
+    if not isinstance(conductivity, (int, float, fd.Constant)):
+        raise NotImplementedError("conductivity must be a constant")
+    pressure_field = _serial(pressure_field)
+    F = _context(pressure_field).boundary_flux(_coefficients(pressure_field), float(conductivity))
+    return {s + 1: float(v) for s, v in enumerate(F)}
+
+
+def mass_transfer_rate(solution: fd.Function, params) -> float:
+    """``T = int beta/mu (p1 - p2) dx``: what network 1 hands to network 2 per unit time (the reference's ``xi``,
+    src/perphil/forms/dpp.py:27, integrated)."""
+    _mixed_pair(solution)
+    solution = _serial(solution)
+    p1, p2 = solution.subfunctions
+    return float(params.beta) / float(params.mu) * (integrate(p1) - integrate(p2))
+
+
+def consistent_fluxes(solution: fd.Function, params) -> fd.Function:
+    """``(r1, r2)`` on W: the residual of the un-eliminated DPP operator, ``r1 = k1/mu K p1 + beta/mu M (p1 - p2)``,
+    ``r2 = k2/mu K p2 - beta/mu M (p1 - p2)`` (``pph_dpp_nodal_flux``).  ``r_f[i]`` is minus the outward flux of network f
+    weighted with the basis function of node i; ``sum(r1) = T = -sum(r2)`` for any field.  Device-resident when `solution`
+    is (no host round trip)."""
+    _mixed_pair(solution)
+    solution = _serial(solution)
+    ctx = _context(solution.sub(0))
+    r = ctx.dpp_nodal_flux(_coefficients(solution), float(params.k1), float(params.k2), float(params.beta), float(params.mu))
+    return fd.Function(solution.function_space(), r, name="consistent_fluxes")
+
+
+@dataclass(frozen=True)
+class MassBalance:
+    """Mass balance of a DPP solution.  ``transfer``: T, network 1 -> 2.  ``outflow_consistent``: per network, minus the sum
+    of the consistent nodal fluxes over the boundary nodes.  ``outflow_direct``: per network, ``boundary_fluxes`` of its
+    pressure with ``k_f / mu``.  ``imbalance``: ``(outflow_consistent[0] + transfer, outflow_consistent[1] - transfer)``,
+    which is the sum of the interior consistent fluxes: rounding for an exactly solved system, the solver's residual
+    otherwise."""
+    transfer: float
+    outflow_consistent: Tuple[float, float]
+    outflow_direct: Tuple[Dict[int, float], Dict[int, float]]
+    imbalance: Tuple[float, float]
+
+
+def mass_balance(solution: fd.Function, params) -> MassBalance:
+    """Transfer, outflows (consistent and by direct integration of the normal flux) and their imbalance; the boundary set
+    is ``Mesh.boundary_nodes(degree)``."""
+    V1, _ = _mixed_pair(solution)
+    solution = _serial(solution)
+    mesh = solution.function_space().mesh()
+    n = solution.function_space().sub(0).local_dim()
+    T = mass_transfer_rate(solution, params)
+    r = consistent_fluxes(solution, params)
+    bnd = mesh.boundary_nodes(V1.degree)
+    if r.on_device:
+        import torch
+
+        t = r.torch()
+        idx = torch.as_tensor(bnd, device=t.device)
+        out = (-float(t[idx].sum()), -float(t[n + idx].sum()))
+    else:
+        v = r.vector()
+        out = (-float(v[bnd].sum()), -float(v[n + bnd].sum()))
+    p1, p2 = solution.subfunctions
+    mu = float(params.mu)
+    direct = (boundary_fluxes(p1, float(params.k1) / mu), boundary_fluxes(p2, float(params.k2) / mu))
+    return MassBalance(T, out, direct, (out[0] + T, out[1] - T))
