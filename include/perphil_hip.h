@@ -389,7 +389,10 @@ int pph_comm_times(pph_ctx* ctx, double* out4);
  * in stencil-ELL storage: one workgroup runs the whole Jacobi-CG of a block solve, the host does not wait for it), out[27] how
  * many of them ended WITHOUT meeting their tolerance (iteration limit, option "onchip_max_it", or p.Ap <= 0; a zero right-hand
  * side counts as converged) - any such solve sets pph_solve_info.inner_failed = 1 and converged = 0: it is reported, not
- * repeated on the host-driven loop - out[28] their CG iterations summed.  All three are 0 when the path did not run. */
+ * repeated on the host-driven loop - out[28] their CG iterations summed.  All three are 0 when the path did not run;
+ * out[29] CG updates of the last solve launched without the next multigrid cycle's pre-smoothed first guess (option
+ * "presmooth_lazy"), out[30] cycles that ran after such an update and formed the guess themselves, out[31] updates that
+ * wrote a guess no cycle read (unpreconditioned-norm CG block solves around the fused cycle; 0 elsewhere). */
 int pph_get_timers(pph_ctx* ctx, double* out, int n);
 /* tuning / profiling switches (no reference counterpart; defaults in brackets):
  *   "op_format" [1]      operator format of the scalar blocks inside block solves / Picard sweeps: 1 stencil-ELL
@@ -428,6 +431,12 @@ int pph_get_timers(pph_ctx* ctx, double* out, int n);
  *   "merge_allreduce" [1] slabs, CG block solves on stencil-ELL operators: the product also sums r.Ap and Ap.Ap, and
  *                        { p.Ap, r.Ap, Ap.Ap, r.r of the previous update } travel in ONE all-reduce; the host forms the next
  *                        r.r by one step of the recurrence (two scalar all-reduces per iteration instead of three)
+ *   "presmooth_lazy" [1] unpreconditioned-norm CG block solves around the fused cycle: a CG update also writes the next
+ *                        cycle's first guess dinv .* r * w (two of its eight vector passes).  1: not when the host expects the
+ *                        update to be the last of its solve - the block's most recent residual contraction would carry the
+ *                        residual below the tolerance; at most two such guesses per solve, none while iteration bodies are
+ *                        replayed from graphs; a cycle that runs after all forms the guess itself, bit for bit the same.
+ *                        2: the update at which the block's previous solve ended.  0: every update writes it
  *   "use_graphs" [1]     launch sequences replayed from captured hipGraphs: ILU(0) sweeps, the launch-only Picard sweeps of
  *                        inner_norm 2, and CG iteration bodies on systems of up to "graph_cg_max_rows" [0] rows (2: always)
  *   "device_scalars" [0] 1: the device-scalar CG branch also over the callback transport (tests)

@@ -758,8 +758,8 @@ class Context:
         return {"halo_ms": t[0], "allreduce_ms": t[1], "halo_timed": int(t[2]), "allreduce_timed": int(t[3])}
 
     def timers(self) -> dict:
-        t = np.zeros(29, dtype=np.float64)
-        self._check(lib.pph_get_timers(self._h, _ptr(t), 29))
+        t = np.zeros(32, dtype=np.float64)
+        self._check(lib.pph_get_timers(self._h, _ptr(t), 32))
         return {"mesh_ms": t[0], "assemble_ms": t[1], "bc_blocks_ms": t[2], "solve_ms": t[3],
                 "spmv_ms": t[4], "spmv_launches": int(t[5]), "spmv_bytes": t[6],
                 "spmv_dot_ms": t[7], "spmv_dot_launches": int(t[8]), "spmv_dot_bytes": t[9],
@@ -773,4 +773,7 @@ class Context:
                 "asm_rows_straight": int(t[23]), "asm_rows_general": int(t[24]), "asm_rows": int(t[25]),
                 # on-chip LU-equivalent block solves of the last solve: how many ran, how many ended short of their tolerance
                 # (iteration limit or p.Ap <= 0; any of them sets SolveInfo.inner_failed), their CG iterations summed
-                "onchip_solves": int(t[26]), "onchip_unconverged": int(t[27]), "onchip_cg_iterations": int(t[28])}
+                "onchip_solves": int(t[26]), "onchip_unconverged": int(t[27]), "onchip_cg_iterations": int(t[28]),
+                # CG updates of the last solve launched without the next cycle's first guess (option presmooth_lazy), cycles
+                # that then formed it themselves, updates that wrote one no cycle read
+                "presmooth_skipped": int(t[29]), "presmooth_late": int(t[30]), "presmooth_unused": int(t[31])}

@@ -679,6 +679,12 @@ int pph_set_option(pph_ctx* ctx, const char* name, double value) {
   if (!strcmp(name, "sell_zwalk_min_chunks")) { ctx->sell_zwalk_min_chunks = (int64_t)value; return PPH_OK; }
   if (!strcmp(name, "graph_cg_max_rows")) { ctx->graph_cg_max_rows = (int64_t)value; la_release_graphs(ctx); return PPH_OK; }
   if (!strcmp(name, "merge_allreduce")) { ctx->merge_allreduce = value != 0.0 ? 1 : 0; return PPH_OK; }
+  if (!strcmp(name, "presmooth_lazy")) {
+    PPH_REQUIRE(ctx, value == 0.0 || value == 1.0 || value == 2.0, "presmooth_lazy: 0 off, 1 residual rule, 2 iteration-count rule");
+    ctx->presmooth_lazy = (int)value;
+    la_release_graphs(ctx);
+    return PPH_OK;
+  }
   if (!strcmp(name, "halo_overlap")) { ctx->halo_overlap = (value == 2.0) ? 2 : (value != 0.0 ? 1 : 0); la_release_graphs(ctx); return PPH_OK; }
   if (!strcmp(name, "halo_overlap_min_rows")) { ctx->halo_overlap_min_rows = (int64_t)value; la_release_graphs(ctx); return PPH_OK; }
   if (!strcmp(name, "sell_xmap")) { ctx->sell_xmap = value != 0; la_release_graphs(ctx); return PPH_OK; }
@@ -859,7 +865,7 @@ int pph_get_timers(pph_ctx* ctx, double* out, int n) {
     (void)hipMemcpyAsync(dst, ctx->D11.state.p, sizeof(dst), hipMemcpyDeviceToHost, ctx->stream);
     (void)hipStreamSynchronize(ctx->stream);
   }
-  const double v[29] = {ctx->t_mesh, ctx->t_asm, ctx->t_bc, ctx->t_solve,
+  const double v[32] = {ctx->t_mesh, ctx->t_asm, ctx->t_bc, ctx->t_solve,
                         ctx->t_spmv[0], (double)ctx->n_spmv[0], ctx->spmv_bytes[0],
                         ctx->t_spmv[1], (double)ctx->n_spmv[1], ctx->spmv_bytes[1], (double)ctx->n_halo,
                         ctx->t_spmv_fine, (double)ctx->n_spmv_fine, ctx->spmv_bytes_fine, (double)ctx->n_split,
@@ -867,8 +873,9 @@ int pph_get_timers(pph_ctx* ctx, double* out, int n) {
                         (double)dn, (double)(ctx->D11.tried ? ctx->D11.ncls : 0), (double)(ctx->D11.on ? dst[1] : ctx->D11.status),
                         ctx->t_dict_build, (double)ctx->n_dict_build, zc11 ? 1.0 : 0.0,
                         ctx->asm_rows_win, ctx->asm_rows_gen, ctx->asm_rows_all,
-                        (double)ctx->onchip_solves, (double)ctx->onchip_unconverged, (double)ctx->onchip_its};
-  for (int i = 0; i < n && i < 29; ++i) out[i] = v[i];
+                        (double)ctx->onchip_solves, (double)ctx->onchip_unconverged, (double)ctx->onchip_its,
+                        (double)ctx->n_presmooth_skipped, (double)ctx->n_presmooth_late, (double)ctx->n_presmooth_unused};
+  for (int i = 0; i < n && i < 32; ++i) out[i] = v[i];
   return PPH_OK;
 }
 

@@ -469,6 +469,10 @@ struct pph_ctx {
   unsigned long long* h_onchip = nullptr;
   int64_t onchip_solves = 0, onchip_unconverged = 0, onchip_its = 0;   // of the last solve (pph_get_timers out[26..28])
   int onchip_max_it = 0;                // iteration limit of an on-chip block solve; 0: 8 n + 64
+  // unpreconditioned-norm CG around the fused cycle (cg_solve_natural): an update the host predicts to be the last of its
+  // solve does not write the next cycle's pre-smoothed first guess; a cycle that runs after all starts with k_cheb_init
+  int presmooth_lazy = 1;               // 0: every update writes it; 1: predicted from the residual contraction; 2: from the block's last iteration count
+  int64_t n_presmooth_skipped = 0, n_presmooth_late = 0, n_presmooth_unused = 0;   // of the last solve (pph_get_timers out[29..31])
   int coarse_on_device = 1;             // coarsest multigrid level (<= 4096 rows): CG inside one workgroup, no host round trips
   int spmv_bench_mode = 0;              // pph_spmv_bench protocol: 0 back-to-back, 1-3 interleaved (see pph_api.hip)
   int64_t mg_replicate_below = 40000;   // slabs: multigrid levels with at most this many global nodes are replicated

@@ -86,10 +86,18 @@ struct MgPre {
   bool launch_only = false;       // the cycle enqueues kernels only (no host decision inside): capturable
 };
 
+// what the unpreconditioned-norm CG of one block remembers from solve to solve within a pph_solve_device call: its updates
+// write the next cycle's first guess only where a cycle is expected to read it (option "presmooth_lazy")
+struct CgMemo {
+  double rho = -1.0;   // most recent observed contraction res_k / res_{k-1} (-1: none yet)
+  int its = -1;        // iterations of the block's previous solve (-1: none yet)
+};
+
 static int cg_solve_natural(pph_ctx* ctx, const Csr& A, const double* b, double* x, const double* dinv, const ApplyFn& pc,
                             double rtol, double atol, int max_it, bool warm, double* r, double* z, double* p, double* q,
                             int slot, KspOut* out, double* hist, int hist_cap, double bnorm_hint, double reduction,
-                            const double* r_init, const MgPre& pre, double rnorm_hint = -1.0, bool first_x0_ready = false) {
+                            const double* r_init, const MgPre& pre, double rnorm_hint = -1.0, bool first_x0_ready = false,
+                            CgMemo* memo = nullptr, bool x_is_zero = false) {
   const int64_t n = A.nrows;
   const Seg sg = pph_owned_seg(A.geom, n);
   auto apply_pc = [&](const double* in, double* o) {
@@ -109,7 +117,7 @@ static int cg_solve_natural(pph_ctx* ctx, const Csr& A, const double* b, double*
     if (r_init) { if (r_init != r) la_copy(ctx, r, r_init, n); }
     else la_spmv_resid(ctx, A, x, b, r);
   } else {
-    la_set(ctx, x, 0.0, n);
+    if (!x_is_zero) la_set(ctx, x, 0.0, n);
     la_copy(ctx, r, b, n);
   }
   double res;
@@ -149,25 +157,28 @@ static int cg_solve_natural(pph_ctx* ctx, const Csr& A, const double* b, double*
     // the two halves of an iteration around the host's convergence test.  `rotate`: r.z (current) := r.z (new) rides
     // on the final reduction of p.Ap - after the direction update read both, before the CG update reads the current one
     bool published = false;   // (the publication of p.Ap and r.r rode on the update's final reduction)
-    auto half_product = [&](bool rotate, bool publish = false) -> int {
+    bool z_ready = false;     // the last update wrote the next cycle's pre-smoothed first guess into z
+    auto half_product = [&](bool rotate, bool publish, bool want_z0) -> int {
       published = false;
+      z_ready = want_z0;
       if (merged) {
         la_spmv_dot3(ctx, A, p, r, q, sE, rotate ? sRZn : -1, sRZc);
         PPH_TRY(la_reduce_device(ctx, sE, 4));
-        la_cg_update_dev(ctx, x, r, p, q, sRZc, sE, n, sE + 3, sg, pre.on ? z : nullptr, pre.dinv, pre.w);   // (its r.r: local, summed with the next product's)
+        la_cg_update_dev(ctx, x, r, p, q, sRZc, sE, n, sE + 3, sg, want_z0 ? z : nullptr, pre.dinv, pre.w);   // (its r.r: local, summed with the next product's)
         return PPH_OK;
       }
       la_spmv_dot(ctx, A, p, q, sPQ, rotate ? sRZn : -1, sRZc, true);   // (its final reduction: inside the update kernel)
       PPH_TRY(la_reduce_device(ctx, sPQ, 1));
       // x += alpha p ; r -= alpha q ; r.r (and the next cycle's pre-smoothed first guess into z)
-      published = la_cg_update_dev(ctx, x, r, p, q, sRZc, sPQ, n, sRR, sg, pre.on ? z : nullptr, pre.dinv, pre.w, -1,
+      published = la_cg_update_dev(ctx, x, r, p, q, sRZc, sPQ, n, sRR, sg, want_z0 ? z : nullptr, pre.dinv, pre.w, -1,
                                    publish ? sPQ : -1, publish ? 2 : 0);
       PPH_TRY(la_reduce_device(ctx, sRR, 1));
       return PPH_OK;
     };
     auto half_direction = [&]() -> int {
       ctx->defer_next_final = true;    // (r.z of the cycle's last kernel: summed inside the direction update)
-      pc_and_rz(z, sRZn, pre.on);
+      if (pre.on && !z_ready) ctx->n_presmooth_late++;   // (the update before was predicted to be the last: k_cheb_init, same bits)
+      pc_and_rz(z, sRZn, z_ready);
       ctx->defer_next_final = false;
       PPH_TRY(la_reduce_device(ctx, sRZn, 1));
       la_p_update_dev(ctx, p, z, sRZn, sRZc, n);                          // p = z + (r.z_new / r.z) p
@@ -190,18 +201,39 @@ static int cg_solve_natural(pph_ctx* ctx, const Csr& A, const double* b, double*
       gk.p[5] = q; gk.p[6] = pre.dinv; gk.p[7] = pre.w;
       gk.n = n; gk.slot = slot; gk.epoch = ctx->mg_epoch; gk.tag = pre.tag;
     }
+    // An update writes z0 = dinv0 .* r * w0 for the cycle of the NEXT iteration - two of its eight vector passes, for
+    // nothing when the solve ends with this update.  The host knows `res` and `tol` before it launches the update: the update
+    // is taken for the last one when the block's most recent contraction would carry `res` below `tol` (presmooth_lazy 2:
+    // when the block's previous solve ended at this iteration), and then passes no z0; if the solve goes on after all, the
+    // cycle forms its first guess itself (k_cheb_init: the same expression in the same order, the same bits; three vector
+    // passes where the update would have spent two).  At most two such guesses per solve - the first rests on the block's
+    // previous solve, the second on this solve's own first contraction; a solve that drifts pays two late starts, not one
+    // per iteration.  The numbers are equal on all ranks.  A replayed body has fixed arguments: no skip there.
+    const bool lazy = ctx->presmooth_lazy && pre.on && memo && !graphable;
+    int guesses = 0;
+    auto want_z0 = [&](int k) -> bool {   // for the update of iteration k (0-based)
+      if (!lazy) return pre.on;
+      bool last = k + 1 >= max_it;
+      if (!last && guesses < 2) {
+        last = (ctx->presmooth_lazy == 2) ? (memo->its == k + 1) : (memo->rho >= 0.0 && res * memo->rho <= tol);
+        guesses += last ? 1 : 0;
+      }
+      if (last) ctx->n_presmooth_skipped++;
+      return !last;
+    };
     int its = 0;
     double rr_prev = res * res;   // (merged all-reduce) r.r the recurrence starts from: host-known before the first update
     while (its < max_it) {
+      const double res_before = res;
       if (its == 0) {
-        PPH_TRY(half_product(false, true));
+        PPH_TRY(half_product(false, true, want_z0(0)));
         if (merged) PPH_TRY(la_fetch_raw(ctx, sRZc, 5));   // r.z (current), p.Ap, r.Ap, Ap.Ap, r.r of the previous update
         else if (published) PPH_TRY(la_wait_published(ctx));
         else PPH_TRY(la_fetch_raw(ctx, sPQ, 2));
       } else {
         auto body = [&]() -> int {
           PPH_TRY(half_direction());
-          PPH_TRY(half_product(true, true));
+          PPH_TRY(half_product(true, true, want_z0(its)));
           if (merged) la_publish(ctx, sRZc, 5);
           else if (!published) la_publish(ctx, sPQ, 2);
           return PPH_OK;
@@ -222,10 +254,13 @@ static int cg_solve_natural(pph_ctx* ctx, const Csr& A, const double* b, double*
       const double pq = ctx->h_scal[sPQ];
       res = std::sqrt(ctx->h_scal[sRR]);
       ++its;
+      if (memo && res_before > 0.0 && res == res) memo->rho = res / res_before;
       if (hist && its < hist_cap) hist[its] = res;
       if (!(pq > 0.0) || !(res == res)) { out->breakdown = true; break; }
       if (res <= tol) { out->converged = true; break; }
     }
+    if (z_ready) ctx->n_presmooth_unused++;   // (the last update's z0: no cycle follows)
+    if (memo) memo->its = its;
     out->its = its;
     out->res = res;
     return PPH_OK;
@@ -269,7 +304,7 @@ static int cg_solve_natural(pph_ctx* ctx, const Csr& A, const double* b, double*
 // ------------------------------------------------------------------------------------------------
 static int cg_solve_fixed(pph_ctx* ctx, const Csr& A, const double* b, double* x, const double* dinv, const ApplyFn& pc,
                           int its, bool warm, double* r, double* z, double* p, double* q, int slot, KspOut* out,
-                          const double* r_init, const MgPre& pre, bool first_x0_ready = false) {
+                          const double* r_init, const MgPre& pre, bool first_x0_ready = false, bool x_is_zero = false) {
   const int64_t n = A.nrows;
   const Seg sg = pph_owned_seg(A.geom, n);
   auto apply_pc = [&](const double* in, double* o) {
@@ -281,7 +316,7 @@ static int cg_solve_fixed(pph_ctx* ctx, const Csr& A, const double* b, double* x
     if (r_init) { if (r_init != r) la_copy(ctx, r, r_init, n); }
     else la_spmv_resid(ctx, A, x, b, r);
   } else {
-    la_set(ctx, x, 0.0, n);
+    if (!x_is_zero) la_set(ctx, x, 0.0, n);
     la_copy(ctx, r, b, n);
   }
   const int sPQ = slot, sRR = slot + 1, sRZn = slot + 2, sRZc = slot + 3;
@@ -317,20 +352,22 @@ static int cg_solve(pph_ctx* ctx, const Csr& A, const double* b, double* x, cons
                     double rtol, double atol, int max_it, bool warm, double* r, double* z, double* p, double* q,
                     int slot, KspOut* out, double* hist, int hist_cap, double bnorm_hint = -1.0,
                     double reduction = 0.0, const double* r_init = nullptr, int norm_type = 0,
-                    const MgPre& pre = MgPre(), double rnorm_hint = -1.0, bool first_x0_ready = false) {
+                    const MgPre& pre = MgPre(), double rnorm_hint = -1.0, bool first_x0_ready = false,
+                    CgMemo* memo = nullptr, bool x_is_zero = false) {   // x_is_zero: a cold solve's x already holds zeros
   const int64_t n = A.nrows;
   if (norm_type == 2 && la_device_scalars(ctx))
-    return cg_solve_fixed(ctx, A, b, x, dinv, pc, max_it, warm, r, z, p, q, slot, out, r_init, pre, first_x0_ready && warm && r_init);
+    return cg_solve_fixed(ctx, A, b, x, dinv, pc, max_it, warm, r, z, p, q, slot, out, r_init, pre, first_x0_ready && warm && r_init,
+                          x_is_zero);
   if (norm_type == 2) {
     // host-scalar transport: the natural-norm loop with an unreachable tolerance does the same iterations
     const int st = cg_solve_natural(ctx, A, b, x, dinv, pc, 0.0, 0.0, max_it, warm, r, z, p, q, slot, out, hist, hist_cap,
-                                    1.0, 0.0, r_init, pre);
+                                    1.0, 0.0, r_init, pre, -1.0, false, nullptr, x_is_zero);
     out->converged = !out->breakdown;
     return st;
   }
   if (norm_type == 1)
     return cg_solve_natural(ctx, A, b, x, dinv, pc, rtol, atol, max_it, warm, r, z, p, q, slot, out, hist, hist_cap,
-                            bnorm_hint, reduction, r_init, pre, rnorm_hint, first_x0_ready && warm && r_init);
+                            bnorm_hint, reduction, r_init, pre, rnorm_hint, first_x0_ready && warm && r_init, memo, x_is_zero);
   // reductions run over the owned entries of a slab (whole vector on a single GPU)
   const Seg sg = pph_owned_seg(A.geom, n);
   const bool fused = (dinv != nullptr) || !pc;
@@ -356,7 +393,7 @@ static int cg_solve(pph_ctx* ctx, const Csr& A, const double* b, double* x, cons
     if (r_init) { if (r_init != r) la_copy(ctx, r, r_init, n); }
     else la_spmv_resid(ctx, A, x, b, r);
   } else {
-    la_set(ctx, x, 0.0, n);
+    if (!x_is_zero) la_set(ctx, x, 0.0, n);
     la_copy(ctx, r, b, n);
     bnorm = -1.0;
   }
@@ -558,6 +595,7 @@ struct BlockSolver {
   bool onchip_used = false;              // an on-chip block solve ran: its record is read when the solve ends
   double bnorm_cache[2] = {-1.0, -1.0};  // ||P^-1 b|| of the first (cold) solve of each block
   double* last_resid = nullptr;          // recurrence residual rhs - A z of the last CG solve (work vector)
+  CgMemo memo[2];                        // per block, of this pph_solve_device call (option "presmooth_lazy")
 
   int setup() {
     A[0] = block_csr(ctx, 0);
@@ -607,7 +645,7 @@ struct BlockSolver {
     return work(ctx, W_IP, (size_t)ctx->n, z0) == PPH_OK;
   }
   int solve(int which, const double* rhs, double* z, bool warm, const double* r_init = nullptr, double* r_io = nullptr,
-            double rnorm_hint = -1.0, bool z0_ready = false) {
+            double rnorm_hint = -1.0, bool z0_ready = false, bool z_is_zero = false) {   // z_is_zero: cold solve, z already zeroed
     last_res = -1.0;
     const int64_t n = ctx->n;
     double *r, *zz, *p, *q;
@@ -675,7 +713,8 @@ struct BlockSolver {
     pre.tag = 16 * ns + which;
     PPH_TRY(cg_solve(ctx, A[which], rhs, z, dinv[which], pc, cfg->inner_rtol, cfg->inner_atol, cfg->inner_max_it,
                      warm, r, zz, p, q, S_INNER, &ko, nullptr, 0, warm ? bnorm_cache[which] : -1.0,
-                     cfg->inner_reduction, warm ? r_init : nullptr, cfg->inner_norm, pre, rnorm_hint, z0_ready));
+                     cfg->inner_reduction, warm ? r_init : nullptr, cfg->inner_norm, pre, rnorm_hint, z0_ready, &memo[which],
+                     z_is_zero && !warm));
     if (!warm) bnorm_cache[which] = ko.bnorm;
     if (cfg->inner_norm == 1) last_res = ko.res;
     last_resid = r;
@@ -749,6 +788,7 @@ int pph_solve_device(pph_ctx* ctx, const pph_solver_cfg* cfg, pph_solve_info* in
   inf.iterations = 0; inf.inner_iterations = 0; inf.converged = 0; inf.inner_failed = 0; inf.resnorm = 0; inf.rhs_norm = 0;
   ctx->coarse_failed = 0;
   ctx->onchip_solves = ctx->onchip_unconverged = ctx->onchip_its = 0;
+  ctx->n_presmooth_skipped = ctx->n_presmooth_late = ctx->n_presmooth_unused = 0;
   la_dot(ctx, ctx->rhs.p, ctx->rhs.p, N, S_A);
   PPH_TRY(la_fetch(ctx, S_A, 1));
   inf.rhs_norm = std::sqrt(ctx->h_scal[S_A]);
@@ -793,8 +833,10 @@ int pph_solve_device(pph_ctx* ctx, const pph_solver_cfg* cfg, pph_solve_info* in
     const int64_t pob = ctx->mesh.own_begin(), pon = ctx->mesh.own_end() - ctx->mesh.own_begin();
     // true residual from direct products only: t12 = A12 du2 and rhs1 = b2 - A21 du1 were formed by SpMVs with
     // the current iterates in this sweep, so two more products (A11 du1, A22 du2) complete it
+    const double* rhs0 = pb;   // right-hand side handed to the macro block's solves
     auto true_residual = [&]() -> int {
       la_sub(ctx, pb, b1, t12, n);
+      rhs0 = pb;
       la_spmv_resid(ctx, bs.A[0], du1, pb, R0);
       la_spmv_resid(ctx, bs.A[1], du2, rhs1, R1);
       la_dot(ctx, R0 + pob, R0 + pob, pon, S_A);
@@ -858,9 +900,13 @@ int pph_solve_device(pph_ctx* ctx, const pph_solver_cfg* cfg, pph_solve_info* in
       // a warm CG block solve starts from its carried residual (R0 / R1) and a cached ||b||: its right-hand side is
       // not read; with the unpreconditioned-norm test the host also knows the residual norms already (hints)
       const bool hints = warm && recur && cfg->inner_norm == 1;
-      if (!(warm && recur)) la_sub(ctx, pb, b1, t12, n);             // rhs of the macro block
-      PPH_TRY(bs.solve(0, pb, du1, warm, (warm && recur) ? R0 : nullptr, recur ? R0 : nullptr, hints ? rn0 : -1.0,
-                       warm && z0r[0]));
+      // rhs of the macro block.  Cold sweep of the CG blocks: t12 = +0, and b - (+0) == b bit for bit (-0 included), so
+      // the solve reads b1 itself instead of a copy; as before, the warm sweeps are handed what the last la_sub left
+      if (!warm && recur) rhs0 = b1;
+      else if (!recur) la_sub(ctx, pb, b1, t12, n);
+      // (cold: du was zeroed above and nothing has written the block since)
+      PPH_TRY(bs.solve(0, rhs0, du1, warm, (warm && recur) ? R0 : nullptr, recur ? R0 : nullptr, hints ? rn0 : -1.0,
+                       warm && z0r[0], !warm));
       double rn1 = -1.0;
       if (warm && recur) {
         // new rhs of the micro block, R1 += rhs1_new - rhs1_old, ||R1||^2 - one pass
@@ -873,7 +919,7 @@ int pph_solve_device(pph_ctx* ctx, const pph_solver_cfg* cfg, pph_solve_info* in
         la_spmv_resid(ctx, A21, du1, b2, rhs1);
       }
       PPH_TRY(bs.solve(1, rhs1, du2, warm, (warm && recur) ? R1 : nullptr, recur ? R1 : nullptr, rn1,
-                       warm && recur && z0p[1] != nullptr));
+                       warm && recur && z0p[1] != nullptr, !warm));
       ++its;
       if (recur) {
         // new coupling term, R0 += A12 du2_old - A12 du2_new, ||R0||^2 - one pass (the first sweep: t12 = 0)
