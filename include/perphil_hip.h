@@ -392,7 +392,11 @@ int pph_comm_times(pph_ctx* ctx, double* out4);
  * repeated on the host-driven loop - out[28] their CG iterations summed.  All three are 0 when the path did not run;
  * out[29] CG updates of the last solve launched without the next multigrid cycle's pre-smoothed first guess (option
  * "presmooth_lazy"), out[30] cycles that ran after such an update and formed the guess themselves, out[31] updates that
- * wrote a guess no cycle read (unpreconditioned-norm CG block solves around the fused cycle; 0 elsewhere). */
+ * wrote a guess no cycle read (unpreconditioned-norm CG block solves around the fused cycle; 0 elsewhere);
+ * out[32] 1 when the last assembly did not store the operator entries of the fine level's straight-line rows (option
+ * "asm_store_values" 0), out[33] launches that wrote such rows because a reader asked, since the context was created,
+ * out[34] levels whose row dictionary was refused on the device while their rows were left out - written by the repair launch
+ * behind that assembly's last check kernel, counted when the solve's end retires the dictionary. */
 int pph_get_timers(pph_ctx* ctx, double* out, int n);
 /* tuning / profiling switches (no reference counterpart; defaults in brackets):
  *   "op_format" [1]      operator format of the scalar blocks inside block solves / Picard sweeps: 1 stencil-ELL
@@ -415,6 +419,14 @@ int pph_get_timers(pph_ctx* ctx, double* out, int n);
  *   "asm_fused" [1]      the node-centred pass writes the eliminated blocks, lifted right-hand side and smoother
  *                        diagonal directly; 0: K and M first, then separate elimination kernels
  *   "asm_keep_km" [0]    1: the fused pass also stores K and M (otherwise they are integrated on demand)
+ *   "asm_store_values" [0] 0: an assembly whose rows are checked against the row dictionaries inside the node kernel
+ *                        (every assembly after the first on a large uniform-coefficient box) computes and compares the
+ *                        operator entries of its straight-line rows but does not store them: the products run on the
+ *                        dictionaries.  The entries are written when somebody needs them - a plain product, pph_get_csr,
+ *                        "sell_dict_poison", a change of the Dirichlet sets or of an "asm_*" option - and, when a check refuses a
+ *                        dictionary on the device, by a launch enqueued behind the check that is empty otherwise
+ *                        (pph_get_timers out[32..34]).  Single context, levels of more than 4096 rows.  1: every assembly
+ *                        stores every entry.  Results are bitwise the same either way
  *   "invalidate_KM"      drop the integrated K and M so that the next assemble integrates again
  *   "mg_fused" [1]       V(1,1) on stencil-ELL levels: fused smoother / transfer kernels + on-chip tail; 0 general cycle
  *   "mg_tail_rows" [5000] levels with at most min(this, 1024) rows join the single-workgroup tail of the cycle

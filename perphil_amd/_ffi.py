@@ -758,8 +758,8 @@ class Context:
         return {"halo_ms": t[0], "allreduce_ms": t[1], "halo_timed": int(t[2]), "allreduce_timed": int(t[3])}
 
     def timers(self) -> dict:
-        t = np.zeros(32, dtype=np.float64)
-        self._check(lib.pph_get_timers(self._h, _ptr(t), 32))
+        t = np.zeros(35, dtype=np.float64)
+        self._check(lib.pph_get_timers(self._h, _ptr(t), 35))
         return {"mesh_ms": t[0], "assemble_ms": t[1], "bc_blocks_ms": t[2], "solve_ms": t[3],
                 "spmv_ms": t[4], "spmv_launches": int(t[5]), "spmv_bytes": t[6],
                 "spmv_dot_ms": t[7], "spmv_dot_launches": int(t[8]), "spmv_dot_bytes": t[9],
@@ -776,4 +776,8 @@ class Context:
                 "onchip_solves": int(t[26]), "onchip_unconverged": int(t[27]), "onchip_cg_iterations": int(t[28]),
                 # CG updates of the last solve launched without the next cycle's first guess (option presmooth_lazy), cycles
                 # that then formed it themselves, updates that wrote one no cycle read
-                "presmooth_skipped": int(t[29]), "presmooth_late": int(t[30]), "presmooth_unused": int(t[31])}
+                "presmooth_skipped": int(t[29]), "presmooth_late": int(t[30]), "presmooth_unused": int(t[31]),
+                # operator values on demand (option asm_store_values 0): the fine level's straight-line rows were not stored by
+                # the last assembly; launches that wrote such rows when a reader asked (since the context was created); levels
+                # whose dictionary was refused on the device while their values were left out (the repair launch wrote them)
+                "asm_values_stale": int(t[32]), "asm_values_materialized": int(t[33]), "asm_store_repairs": int(t[34])}

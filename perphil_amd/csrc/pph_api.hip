@@ -165,6 +165,7 @@ static void release_system(pph_ctx* ctx) {
 static void free_system(pph_ctx* ctx) {
   ctx->A11.release(); ctx->A22.release(); ctx->A12.release(); ctx->A21.release();
   ctx->E11.release(); ctx->E22.release(); ctx->E12.release(); ctx->E21.release();
+  ctx->vals0 = ValuesState();   // (the values are gone: nothing to write on demand)
   ctx->D11.release(); ctx->D22.release(); ctx->D12.release(); ctx->DG.release();
   ctx->rhs.release(); ctx->u0.release(); ctx->sol.release();
   ctx->mrowptr.release(); ctx->mcol.release(); ctx->mval.release();
@@ -330,6 +331,8 @@ int pph_get_coords(pph_ctx* ctx, double* coords_host) {
 // range; mask and boundary-value vector of `field` are rebuilt from them on the context stream
 static int dirichlet_apply(pph_ctx* ctx, int field, const int64_t* dn, const double* dv, int64_t count) {
   const int64_t n = ctx->n;
+  // operator values the last assembly left to be written on demand: written now, while the masks they were computed for stand
+  PPH_TRY(sell_values_ensure(ctx, -1));
   release_system(ctx);  // any assembled system is stale now
   PPH_HIP(ctx, hipMemsetAsync(ctx->g[field].p, 0, sizeof(double) * (size_t)n, ctx->stream));
   const int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
@@ -622,6 +625,15 @@ int pph_spmv_bench(pph_ctx* ctx, int which, int reps, double* avg_ms) {
 int pph_set_option(pph_ctx* ctx, const char* name, double value) {
   if (!ctx || !name) return PPH_ERR_INVALID;
   la_release_graphs(ctx);   // captured iteration bodies were recorded under the old settings
+  if (!strcmp(name, "asm_store_values")) { ctx->asm_store_values = value != 0.0 ? 1 : 0; return PPH_OK; }
+  // test aid: readers take the stored values as the last assembly left them (under asm_poison: NaNs in the rows it did not store)
+  if (!strcmp(name, "asm_values_peek")) { ctx->values_peek = value != 0.0 ? 1 : 0; return PPH_OK; }
+  // Options that change which assembly path runs, its wave map or the storage format: operator values left to be written on
+  // demand are written first, by the launch they were left out of.  Not asm_poison (it only fills outputs ahead of the next
+  // assembly) and not invalidate_KM, which every benchmark step sets: the launch that writes the values takes nothing from K or M.
+  if ((!strncmp(name, "asm_", 4) && strcmp(name, "asm_poison")) || !strcmp(name, "sell_sym") || !strcmp(name, "sell_sym_slabs") ||
+      !strcmp(name, "op_format"))
+    PPH_TRY(sell_values_ensure(ctx, -1));
   if (!strcmp(name, "spmv_lanes")) {
     const int v = (int)value;
     PPH_REQUIRE(ctx, v == 0 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64, "spmv_lanes must be 0,4,8,16,32,64");
@@ -752,6 +764,7 @@ int pph_set_option(pph_ctx* ctx, const char* name, double value) {
     // tests: mark the dictionaries of the fine blocks as failed ON THE DEVICE only, as a failed re-assembly check would -
     // the products launched for them must then take the stored values (the plain path inside the dictionary kernel)
     static const int bad = -2;
+    PPH_TRY(sell_values_ensure(ctx, -1));   // (the host is not told: the products fall back to stored values no repair launch will write)
     for (SellDict* D : {&ctx->D11, &ctx->D22, &ctx->D12})
       if (D->state.p) PPH_HIP(ctx, hipMemcpyAsync(D->state.p + 1, &bad, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -809,6 +822,7 @@ int pph_comm_set_callbacks(pph_ctx* ctx, int rank, int world, pph_halo_fn halo, 
   if (!ctx) return PPH_ERR_INVALID;
   PPH_REQUIRE(ctx, world >= 1 && rank >= 0 && rank < world, "rank %d outside world %d", rank, world);
   PPH_REQUIRE(ctx, world == 1 || (halo && allreduce), "multi-rank contexts need both callbacks");
+  PPH_TRY(sell_values_ensure(ctx, -1));
   comm_release(ctx);
   ctx->rank = rank;
   ctx->world = world;
@@ -865,7 +879,7 @@ int pph_get_timers(pph_ctx* ctx, double* out, int n) {
     (void)hipMemcpyAsync(dst, ctx->D11.state.p, sizeof(dst), hipMemcpyDeviceToHost, ctx->stream);
     (void)hipStreamSynchronize(ctx->stream);
   }
-  const double v[32] = {ctx->t_mesh, ctx->t_asm, ctx->t_bc, ctx->t_solve,
+  const double v[35] = {ctx->t_mesh, ctx->t_asm, ctx->t_bc, ctx->t_solve,
                         ctx->t_spmv[0], (double)ctx->n_spmv[0], ctx->spmv_bytes[0],
                         ctx->t_spmv[1], (double)ctx->n_spmv[1], ctx->spmv_bytes[1], (double)ctx->n_halo,
                         ctx->t_spmv_fine, (double)ctx->n_spmv_fine, ctx->spmv_bytes_fine, (double)ctx->n_split,
@@ -874,8 +888,9 @@ int pph_get_timers(pph_ctx* ctx, double* out, int n) {
                         ctx->t_dict_build, (double)ctx->n_dict_build, zc11 ? 1.0 : 0.0,
                         ctx->asm_rows_win, ctx->asm_rows_gen, ctx->asm_rows_all,
                         (double)ctx->onchip_solves, (double)ctx->onchip_unconverged, (double)ctx->onchip_its,
-                        (double)ctx->n_presmooth_skipped, (double)ctx->n_presmooth_late, (double)ctx->n_presmooth_unused};
-  for (int i = 0; i < n && i < 32; ++i) out[i] = v[i];
+                        (double)ctx->n_presmooth_skipped, (double)ctx->n_presmooth_late, (double)ctx->n_presmooth_unused,
+                        ctx->vals0.stale ? 1.0 : 0.0, (double)ctx->n_values_materialized, (double)ctx->n_store_repairs};
+  for (int i = 0; i < n && i < 35; ++i) out[i] = v[i];
   return PPH_OK;
 }
 

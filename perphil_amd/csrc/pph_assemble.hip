@@ -648,51 +648,7 @@ __global__ __launch_bounds__(256) void k_elem_rows(const int32_t* __restrict__ c
 #undef sG
 #undef sW
 
-// Operands of the fused epilogue of k_gather_rows<DIM, true>: at the point where a CSR entry (K_ij, M_ij) of a
-// complete row is known, the Dirichlet-eliminated DPP blocks, the lifted right-hand side and the smoother's
-// diagonal / spectral bound of both diagonal blocks are formed from it directly, instead of writing K and M and
-// streaming them again through k_lift_rhs, k_blocks and k_diag_lam.
-struct FuseArgs {
-  const uint8_t *m1, *m2, *near;
-  const double *g1, *g2;
-  double a, b, c;
-  double *A11, *A22, *A12, *A21;   // A21 null: aliased to A12 (same Dirichlet set on both fields)
-  double *rhs, *u0;                // [2n]
-  double *dinv1, *dinv2;           // [n] each
-  unsigned long long* lam;         // [2] max_i sum_j |a_ij| / |a_ii| as the bit pattern of a non-negative double
-  int keep_km;                     // also store K and M
-  int same;                        // both fields carry the same Dirichlet set (one mask gather per entry)
-  // ld > 0: A11 .. A21 are stencil-ELL arrays (pph_sell.hip): entry (row, column row + (dx,dy,dz)) is stored at
-  // [slot_of[(dz+1)*9 + (dy+1)*3 + (dx+1)] * ld + row]; ld == 0: CSR value arrays addressed by the pattern position
-  // With symmetric storage (Sell::sym) only the diagonal and the upper slots are stored: slot_of is then the STORED
-  // slot (s - S/2) or -1 for a lower slot, whose entry is not written.  The diagonal blocks (slot_of) and the coupling
-  // blocks (slot_of_c: symmetric only when both fields carry the same Dirichlet set) have their own tables.
-  int symg;                        // symmetric storage on a slab: ghost rows keep their entries towards owned columns
-  int64_t ld;
-  int8_t slot_of[27];
-  int8_t slot_of_c[27];
-  // k_asm_node2 on a uniform box (MeshData::uniform): the canonical edge lengths the cells are integrated on
-  double hcan[3] = {0, 0, 0};
-  // k_asm_node2, listed mode: row i of the (mini) output is the row of node list[i]
-  const uint32_t* list = nullptr;
-  // k_asm_node2, check mode (row dictionaries, pph_sell.hip "check fused into the assembly"): class arrays, tables and status
-  // words of the operators this launch writes (0: A11, 1: A22, 2: A12; null: no dictionary), the alarm word of the context
-  const uint16_t* dcls[3] = {nullptr, nullptr, nullptr};
-  const double* dtab[3] = {nullptr, nullptr, nullptr};
-  int* dstate[3] = {nullptr, nullptr, nullptr};
-  int dn[3] = {0, 0, 0};
-  int* alarm = nullptr;
-  // k_asm_node2 in two launches, k_n2_check_general: the wave map that follows the grid lines (WaveMap; n2_wave).  Null: a
-  // wave is 64 consecutive aligned rows
-  const uint32_t* wm_win = nullptr;
-  const uint32_t* wm_pairs = nullptr;
-  int wm_nwin = 0, wm_ngen = 0;
-  // host side only: that map's owner (built on first use); the group and dictionaries behind the check, and the views they describe
-  WaveMap* wm = nullptr;
-  DictGroup* G = nullptr;
-  SellDict* dicts[3] = {nullptr, nullptr, nullptr};
-  const Sell* views[3] = {nullptr, nullptr, nullptr};
-};
+// (struct FuseArgs, the operands of the fused epilogues: pph_internal.h)
 
 // Eliminated entries of the fused epilogues.  rm / cm: mask bytes of the row and of the column dof (bit 0 constrained,
 // bit 1 ghost plane of a slab).  Ghost rows belong to the neighbouring slab and are empty here - except, with
@@ -1427,11 +1383,14 @@ static int blocks_alloc_sell(pph_ctx* ctx) {
   // diagonal blocks: symmetric after the symmetric elimination; coupling blocks: A21 = A12^T, and A12 itself is
   // symmetric only when both fields carry the same Dirichlet set (then A21 is not stored at all)
   const int sym = pph_sell_sym(ctx), sym_c = (sym && ctx->a21_alias) ? 1 : 0;
+  const double* const was[4] = {ctx->E11.p, ctx->E22.p, ctx->E12.p, ctx->E21.p};
   PPH_TRY(sell_alloc(ctx, ctx->mesh, ctx->E11, &ctx->S11, sym));
   PPH_TRY(sell_alloc(ctx, ctx->mesh, ctx->E22, &ctx->S22, sym));
   PPH_TRY(sell_alloc(ctx, ctx->mesh, ctx->E12, &ctx->S12, sym_c));
   if (ctx->a21_alias) { ctx->E21.release(); ctx->S21 = ctx->S12; }
   else PPH_TRY(sell_alloc(ctx, ctx->mesh, ctx->E21, &ctx->S21, 0));
+  // (arrays allocated anew: what was known about the old ones' contents goes with them)
+  if (was[0] != ctx->E11.p || was[1] != ctx->E22.p || was[2] != ctx->E12.p || was[3] != ctx->E21.p) ctx->vals0 = ValuesState();
   return PPH_OK;
 }
 
@@ -1517,6 +1476,7 @@ int pph_launch_blocks(pph_ctx* ctx, int monolithic) {
     PPH_TRY(sell_from_csr(ctx, ctx->mesh, ctx->A12.p, ctx->E12, &ctx->S12, sym_c));
     if (ctx->a21_alias) { ctx->E21.release(); ctx->S21 = ctx->S12; }
     else PPH_TRY(sell_from_csr(ctx, ctx->mesh, ctx->A21.p, ctx->E21, &ctx->S21, 0));
+    ctx->vals0 = ValuesState();   // (written completely, by another path: nothing stale, nothing a later assembly may leave out)
     ctx->ell_ok = true;
   }
   return blocks_mono(ctx, monolithic);
@@ -2412,7 +2372,10 @@ __device__ __forceinline__ void n2_store_pair(char* base, uint32_t offp, bool od
 // 0 / 1 integers combined with & | ^ (C++'s && would come back as exec-mask regions with the loads sunk into them).
 // SAME: both fields carry one Dirichlet set (m1 == m2): one predicate per entry position instead of four.
 // MODE 1: every stored entry is compared with the stored half of its class's table row (LDS; fact A of the fused dictionary
-// check); MODE 2 (listed): only the operator entries are produced
+// check); MODE 2 (listed): only the operator entries are produced; MODE 4: MODE 1 without the operator stores (the row is
+// computed and compared as before, dinv / rhs / u0 / the spectral bound are written - only A11 .. A21 are not: while the
+// dictionaries stand no product reads them, ValuesState in pph_internal.h); MODE 5: MODE 2 on the rows of this launch's
+// wave map instead of a list (what MODE 4 left out, written on demand: n2_launch_values)
 template <int DIM, bool FAST, bool SAME, bool SYM, bool SYMC, bool HAS12, bool HAS21, bool HASRHS, int MODE>
 __device__ __forceinline__ void n2_epilogue(const double (&kv)[DIM == 3 ? 27 : 9], const double (&mv)[DIM == 3 ? 27 : 9],
                                             const unsigned (&hasb)[DIM][2], int px, int py, int64_t n, const FuseArgs& fa,
@@ -2444,11 +2407,12 @@ __device__ __forceinline__ void n2_epilogue(const double (&kv)[DIM == 3 ? 27 : 9
   // 64 rows of the wave are of ONE class per operator (every interior wave of a uniform box) - the table row is wave-uniform
   // and comes through scalar loads from the global table (c11 .. c12 are then the wave's classes); MODE 1: per-lane rows from LDS.
   constexpr int SSC = NSLOT / 2 + 1;
-  constexpr bool CHK = (MODE == 1 || MODE == 3);
+  constexpr bool CHK = (MODE == 1 || MODE == 3 || MODE == 4);
+  constexpr bool STORE = MODE != 4;
   const bool chk12 = CHK && SYMC && HAS12 && fa.dcls[2] != nullptr;
   const double *tr11 = nullptr, *tr22 = nullptr, *tr12 = nullptr;
   unsigned long long acc11 = 0ull, acc22 = 0ull, acc12 = 0ull;
-  if (MODE == 1) {
+  if (MODE == 1 || MODE == 4) {
     tr11 = stab + c11 * SSC;
     tr22 = stab + fa.dn[0] * SSC + c22 * SSC;
     tr12 = stab + (fa.dn[0] + fa.dn[1]) * SSC + (chk12 ? c12 : 0) * SSC;
@@ -2498,8 +2462,8 @@ __device__ __forceinline__ void n2_epilogue(const double (&kv)[DIM == 3 ? 27 : 9
       acc22 |= (unsigned long long)(__double_as_longlong(o22) ^ __double_as_longlong(tr22[so]));
     }
     if (CHK && SYMC && HAS12 && sc >= 0) acc12 |= (unsigned long long)(__double_as_longlong(o12) ^ __double_as_longlong(tr12[sc]));
-    if (so >= 0) n2_store_pair(pD + so * ldb, offp, odd, o11, o22);
-    if (sc >= 0 && HAS12) {
+    if (STORE && so >= 0) n2_store_pair(pD + so * ldb, offp, odd, o11, o22);
+    if (STORE && sc >= 0 && HAS12) {
       if (HAS21) {
         n2_store_pair(pC + sc * ldb, offp, odd, o12, o21);
       } else if ((sc & 1) == 0 && sc + 1 < NSC) {
@@ -2526,7 +2490,7 @@ __device__ __forceinline__ void n2_epilogue(const double (&kv)[DIM == 3 ? 27 : 9
       if (fa.alarm) __hip_atomic_store(fa.alarm, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
-  if (MODE == 2) return;                       // listed mode: operator entries only
+  if (MODE == 2 || MODE == 5) return;          // listed mode / values on demand: operator entries only
   const double i1 = (d11 != 0.0) ? 1.0 / d11 : 1.0, i2 = (d22 != 0.0) ? 1.0 / d22 : 1.0;
   const double q1 = t11 * fabs(i1), q2 = t22 * fabs(i2);
   best1 = (own1 && q1 > best1) ? q1 : best1;   // (ghost rows: not rows of this rank's operator)
@@ -2694,10 +2658,15 @@ static int n2_wave_map_ensure(pph_ctx* ctx, const MeshData& mesh, const uint8_t*
   return PPH_OK;
 }
 
+// workgroups per CU the register budget is set for: three for the plain straight-line launch.  The check modes (1, and 4 = 1
+// without the operator stores) and the values-only launch (5) keep two: on a uniform box mode 4 needs 142 registers (mode 1:
+// 146) and runs three workgroups per CU under either bound; with coordinate loads a bound of three makes modes 4 and 5 spill
+// (136 - 264 and 44 bytes of scratch per lane), so it was not taken
+constexpr int n2_min_blocks(int path, int mode) { return (path == 1 && mode == 0) ? 3 : 2; }
 // PATH 0: both bodies in one kernel; 1: only the waves that take the straight-line body, 2: only the others (two
 // launches with separate register allocations; measured against PATH 0)
 template <int DIM, bool SYM, bool SYMC, bool HAS12, bool HAS21, bool HASRHS, bool SAME, int PATH, int MODE = 0, bool UNI = false>
-__global__ __launch_bounds__(256, (PATH == 1 && MODE != 1) ? 3 : 2) void k_asm_node2(const double* __restrict__ cx, const double* __restrict__ cy,
+__global__ __launch_bounds__(256, n2_min_blocks(PATH, MODE)) void k_asm_node2(const double* __restrict__ cx, const double* __restrict__ cy,
                                                       const double* __restrict__ cz, int nx, int ny, int nzl, int px, int py,
                                                       int pz, int64_t n, FuseArgs fa, int xmap) {
   constexpr int NSLOT = (DIM == 3) ? 27 : 9;
@@ -2705,7 +2674,16 @@ __global__ __launch_bounds__(256, (PATH == 1 && MODE != 1) ? 3 : 2) void k_asm_n
   // (the timing probes of DESIGN.md section 4.2 - no operator stores, synthetic coordinates - were runtime flags: every flag
   // test splits the straight-line code; removed after measuring)
   extern __shared__ double n2_stab[];
-  if (MODE == 1) {
+  if (MODE == 5 && fa.guard) {
+    // repair after a check-mode assembly that did not store (MODE 4): nothing to do unless one of the level's dictionaries
+    // was refused on the device - every workgroup leaves here, before any barrier (the status words are wave-uniform)
+    bool refused = false;
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+      if (fa.dstate[d]) refused = refused || fa.dstate[d][1] < 0;
+    if (!refused) return;
+  }
+  if (MODE == 1 || MODE == 4) {
     // stored halves of the dictionaries' tables -> LDS: [A11 classes][A22 classes][A12 classes] x (NSLOT / 2 + 1)
     constexpr int SSC = NSLOT / 2 + 1, C0 = NSLOT / 2;
     int base = 0;
@@ -2757,7 +2735,7 @@ __global__ __launch_bounds__(256, (PATH == 1 && MODE != 1) ? 3 : 2) void k_asm_n
     // its table rows through scalar loads - was built beside the per-lane LDS rows: two epilogues in one kernel spill 0.6 - 1.3 KB
     // per lane; the LDS rows alone are cheap enough)
     int c11 = 0, c22 = 0, c12 = 0;
-    if (MODE == 1) {
+    if (MODE == 1 || MODE == 4) {
       const bool has12 = SYMC && HAS12 && fa.dcls[2] != nullptr;
       c11 = fa.dcls[0][node]; c22 = fa.dcls[1][node]; c12 = has12 ? (int)fa.dcls[2][node] : 0;
     }
@@ -2773,7 +2751,7 @@ __global__ __launch_bounds__(256, (PATH == 1 && MODE != 1) ? 3 : 2) void k_asm_n
                                                                             best1, best2, n2_stab, c11, c22, c12);
     }
   }
-  if (MODE != 2) fuse_lam_max(best1, best2, fa.lam);
+  if (MODE != 2 && MODE != 5) fuse_lam_max(best1, best2, fa.lam);
 }
 
 // Fact A of the fused dictionary check for the rows of the GENERAL-form waves: the straight-line launch compares what it
@@ -2898,6 +2876,60 @@ bool pph_can_fuse_assembly(const pph_ctx* ctx) {
   return ctx->asm_kernel != 0;   // simplices: the node-centred gather kernel
 }
 
+// The operator entries of the straight-line rows of a level, and nothing else (k_asm_node2 MODE 5): what a check-mode assembly
+// that did not store them (MODE 4) left out, from that assembly's own arguments - same source, same roundings, same bits as
+// the storing launch (the overlapping windows of the wave map already rely on that).  fr.guard 1: the repair enqueued behind the
+// level's last check kernel, an empty grid unless a dictionary was refused on the device; 0: sell_values_ensure.
+static int n2_launch_values(pph_ctx* ctx, const MeshData& mesh, const FuseArgs& fr, int variant, bool uni) {
+  const int pz = mesh.kind == PPH_CELL_QUAD ? 1 : mesh.pzl, nz = mesh.kind == PPH_CELL_QUAD ? 0 : mesh.nzl;
+  const int64_t nb = fr.wm_win ? ((ceil_div64(fr.wm_nwin, 4) + 7) / 8) * 8 : ((ceil_div64(mesh.n, 256) + 7) / 8) * 8;
+  const int grid = (int)(nb < 8 ? 8 : (nb < 256 * 64 ? nb : 256 * 64));
+#define PPH_N2V(DIMV, SC, H12, H21, SM, UNIV)                                                                                   \
+  hipLaunchKernelGGL((k_asm_node2<DIMV, true, SC, H12, H21, false, SM, 1, 5, UNIV>), dim3(grid), dim3(256), 0, ctx->stream,     \
+                     mesh.cx.p, mesh.cy.p, mesh.cz.p, mesh.nx, mesh.ny, nz, mesh.px, mesh.py, pz, mesh.n, fr, ctx->asm_node_xmap)
+#define PPH_N2V_DIM(DIMV, UNIV)                                          \
+  switch (variant) {                                                     \
+    case 0: PPH_N2V(DIMV, true, false, false, true, UNIV); break;        \
+    case 2: PPH_N2V(DIMV, true, true, false, true, UNIV); break;         \
+    case 4: PPH_N2V(DIMV, false, true, true, false, UNIV); break;        \
+    case 6: PPH_N2V(DIMV, true, false, false, false, UNIV); break;       \
+    default: pph_set_error(ctx, "operator values on demand: no kernel for storage variant %d", variant); return PPH_ERR_INVALID; \
+  }
+  if (mesh.kind == PPH_CELL_QUAD) { if (uni) { PPH_N2V_DIM(2, true) } else { PPH_N2V_DIM(2, false) } }
+  else { if (uni) { PPH_N2V_DIM(3, true) } else { PPH_N2V_DIM(3, false) } }
+#undef PPH_N2V_DIM
+#undef PPH_N2V
+  PPH_HIP(ctx, hipGetLastError());
+  return PPH_OK;
+}
+
+// The one place that makes stored operator values whole again (ValuesState): every reader of them that is not a dictionary
+// product comes through here, and so does every entry point that is about to change an input of the assembly while values
+// are stale - "stale" then always means "can be written now, bit for bit".  level < 0: every level.
+int sell_values_ensure(pph_ctx* ctx, int level) {
+  if (ctx->values_peek) return PPH_OK;
+  const int nlev = ctx->mg.empty() ? 1 : (int)ctx->mg.size();   // (level 0: the context's blocks, with or without a hierarchy)
+  for (int l = (level < 0 ? 0 : level); l < (level < 0 ? nlev : level + 1) && l < nlev; ++l) {
+    ValuesState& V = l == 0 ? ctx->vals0 : ctx->mg[(size_t)l].vals;
+    if (!V.stale) continue;
+    FuseArgs fr = V.last;
+    fr.guard = 0;
+    PPH_TRY(n2_launch_values(ctx, l == 0 ? ctx->mesh : ctx->mg[(size_t)l].mesh, fr, V.variant, V.uni));
+    V.stale = false;
+    ctx->n_values_materialized++;
+  }
+  return PPH_OK;
+}
+int sell_values_ensure_for(pph_ctx* ctx, const double* val) {
+  if (!val) return PPH_OK;
+  const int nlev = ctx->mg.empty() ? 1 : (int)ctx->mg.size();
+  for (int l = 0; l < nlev; ++l) {
+    const ValuesState& V = l == 0 ? ctx->vals0 : ctx->mg[(size_t)l].vals;
+    if (V.stale && (val == V.last.A11 || val == V.last.A22 || val == V.last.A12 || val == V.last.A21)) return sell_values_ensure(ctx, l);
+  }
+  return PPH_OK;
+}
+
 // element rows (multilinear cells) + the fused node-centred pass on any level mesh
 int pph_launch_fused_kernels(pph_ctx* ctx, MeshData& mesh, const FuseArgs& fa, double* Kp, double* Mp) {
   const bool multilinear = (mesh.kind == PPH_CELL_QUAD || mesh.kind == PPH_CELL_HEX);
@@ -2907,6 +2939,13 @@ int pph_launch_fused_kernels(pph_ctx* ctx, MeshData& mesh, const FuseArgs& fa, d
                            ((ctx->asm_node && ctx->asm_affine && mesh.all_affine && !ctx->asm_tile_probe && mesh.n < ((int64_t)1 << 29)) ||
                             ctx->asm_tile == 2 || mesh.n >= ctx->asm_tile_min_nodes);
   if (fa.ld == 0 || fa.keep_km || !closed_form) PPH_TRY(pph_ensure_pattern(ctx, mesh));
+  // every path below writes every row of A11 .. A21 - except the check-mode node assembly that is allowed not to (nostore)
+  ValuesState* const vs = fa.ld != 0 ? fa.vs : nullptr;
+  const bool whole = vs && vs->base[0] == fa.A11 && vs->base[1] == fa.A22 && vs->base[2] == fa.A12 && vs->base[3] == fa.A21;
+  if (vs) {
+    vs->stale = false;
+    vs->base[0] = fa.A11; vs->base[1] = fa.A22; vs->base[2] = fa.A12; vs->base[3] = fa.A21;
+  }
   if (!multilinear) {
     int64_t nbs = ceil_div64(mesh.n, 256);
     const int gs = (int)(nbs < 256 * 32 ? nbs : 256 * 32);
@@ -2990,6 +3029,13 @@ int pph_launch_fused_kernels(pph_ctx* ctx, MeshData& mesh, const FuseArgs& fa, d
         }
         fc.alarm = ctx->dict_alarm_dev;
       }
+      // Operator values on demand (option asm_store_values 0): with the check fused into this assembly the products that
+      // follow run on the dictionaries and read no stored value, so the straight-line launch computes and compares its rows
+      // but does not store them (MODE 4).  Only arrays a storing assembly wrote completely, only on one context (slabs keep
+      // storing), and not on the small levels whose values single-workgroup kernels read whatever the dictionaries say (on-chip
+      // CG: up to 4096 rows; the multigrid tail: coarse levels of up to mg_tail_rows).
+      const bool nostore = fuse && !ctx->asm_store_values && ctx->world == 1 && whole && mesh.n > 4096 &&
+                           (&mesh == &ctx->mesh || mesh.n > ctx->mg_tail_rows);
       if (ctx->asm_poison) {
         // test aid: every output row of the level starts as NaNs (all bits set), so that a row no wave stores shows
         const int ns = mesh.kind == PPH_CELL_QUAD ? 9 : 27;
@@ -3015,7 +3061,7 @@ int pph_launch_fused_kernels(pph_ctx* ctx, MeshData& mesh, const FuseArgs& fa, d
         if (&mesh == &ctx->mesh) { ctx->asm_rows_win = (double)W.rows_win; ctx->asm_rows_gen = (double)W.rows_gen; }
       }
 #define PPH_N2P(DIMV, S, SC, H12, H21, HR, SM, PATHV, MODEV, UNIV)                                                                      \
-      hipLaunchKernelGGL((k_asm_node2<DIMV, S, SC, H12, H21, HR, SM, PATHV, MODEV, UNIV>), dim3(gridp[PATHV]), dim3(256), MODEV == 1 ? lds : 0,    \
+      hipLaunchKernelGGL((k_asm_node2<DIMV, S, SC, H12, H21, HR, SM, PATHV, MODEV, UNIV>), dim3(gridp[PATHV]), dim3(256), (MODEV == 1 || MODEV == 4) ? lds : 0,    \
                          ctx->stream, mesh.cx.p, mesh.cy.p, mesh.cz.p, mesh.nx, mesh.ny, nz, mesh.px, mesh.py, pz, mesh.n, fc,           \
                          ctx->asm_node_xmap)
 #define PPH_N2(DIMV, S, SC, H12, H21, HR, SM, UNIV)                                                        \
@@ -3029,7 +3075,8 @@ int pph_launch_fused_kernels(pph_ctx* ctx, MeshData& mesh, const FuseArgs& fa, d
       // (check mode exists for the symmetric-storage variants in two launches only: what a dictionary needs anyway)
 #define PPH_N2C(DIMV, S, SC, H12, H21, HR, SM, UNIV)                                                       \
       do {                                                                                                  \
-        PPH_N2P(DIMV, S, SC, H12, H21, HR, SM, 1, 1, UNIV);                                                 \
+        if (nostore) PPH_N2P(DIMV, S, SC, H12, H21, HR, SM, 1, 4, UNIV);                                    \
+        else PPH_N2P(DIMV, S, SC, H12, H21, HR, SM, 1, 1, UNIV);                                            \
         PPH_N2P(DIMV, S, SC, H12, H21, HR, SM, 2, 0, UNIV);                                                 \
         hipLaunchKernelGGL(k_n2_check_general<DIMV>, dim3(gridp[2]), dim3(256), lds, ctx->stream, mesh.px, mesh.py, pz, mesh.n, fc); \
       } while (0)
@@ -3051,6 +3098,19 @@ int pph_launch_fused_kernels(pph_ctx* ctx, MeshData& mesh, const FuseArgs& fa, d
 #undef PPH_N2
 #undef PPH_N2P
       PPH_HIP(ctx, hipGetLastError());
+      if (nostore) {
+        // a refusal is found on the device, by a wave of the straight-line launch or by k_n2_check_general, with the products
+        // already enqueued: behind the level's last check kernel one guarded launch that writes the missing rows if - and only
+        // if - a status word went negative.  The host keeps the arguments: sell_values_ensure writes them when somebody asks.
+        vs->stale = true;
+        vs->last = fc;
+        vs->last.vs = nullptr; vs->last.G = nullptr; vs->last.wm = nullptr;
+        vs->variant = variant;
+        vs->uni = uni;
+        FuseArgs fr = vs->last;
+        fr.guard = 1;
+        PPH_TRY(n2_launch_values(ctx, mesh, fr, variant, uni));
+      }
       return PPH_OK;
     }
   }
@@ -3129,9 +3189,10 @@ int pph_launch_fused_kernels(pph_ctx* ctx, MeshData& mesh, const FuseArgs& fa, d
 int pph_launch_level_operators(pph_ctx* ctx, MeshData& mesh, const uint8_t* m1, const uint8_t* m2, const uint8_t* near,
                                int same, double coefK1, double coefK2, double coefM, double* A1, double* A2,
                                double* dinv1, double* dinv2, unsigned long long* lam, int64_t ell_ld, int ell_sym,
-                               DictGroup* group, SellDict* dicts, const Sell* views, WaveMap* wmap) {
+                               DictGroup* group, SellDict* dicts, const Sell* views, WaveMap* wmap, ValuesState* vstate) {
   FuseArgs fa;
   fa.wm = wmap;
+  fa.vs = vstate;
   if (group && dicts && views) {
     fa.G = group;
     for (int d = 0; d < 2; ++d) { fa.dicts[d] = &dicts[d]; fa.views[d] = &views[d]; }
@@ -3189,6 +3250,7 @@ int pph_launch_assemble_fused(pph_ctx* ctx, int monolithic) {
   fa.same = ctx->a21_alias ? 1 : 0;
   fa.wm = &ctx->wmap;
   if (ell) {
+    fa.vs = &ctx->vals0;
     fa.G = &ctx->DG;
     fa.dicts[0] = &ctx->D11; fa.dicts[1] = &ctx->D22; fa.dicts[2] = &ctx->D12;
     fa.views[0] = &ctx->S11; fa.views[1] = &ctx->S22; fa.views[2] = &ctx->S12;

@@ -145,6 +145,67 @@ static inline int sell_slots(int kind) {
 static inline int sell_stored(int kind, int sym) { return sym ? sell_slots(kind) / 2 + 1 : sell_slots(kind); }
 static inline int64_t sell_ld(int64_t n) { return (n + 63) & ~(int64_t)63; }
 
+struct ValuesState;
+// Operands of the fused epilogue of k_gather_rows<DIM, true>: at the point where a CSR entry (K_ij, M_ij) of a
+// complete row is known, the Dirichlet-eliminated DPP blocks, the lifted right-hand side and the smoother's
+// diagonal / spectral bound of both diagonal blocks are formed from it directly, instead of writing K and M and
+// streaming them again through k_lift_rhs, k_blocks and k_diag_lam.
+struct FuseArgs {
+  const uint8_t *m1, *m2, *near;
+  const double *g1, *g2;
+  double a, b, c;
+  double *A11, *A22, *A12, *A21;   // A21 null: aliased to A12 (same Dirichlet set on both fields)
+  double *rhs, *u0;                // [2n]
+  double *dinv1, *dinv2;           // [n] each
+  unsigned long long* lam;         // [2] max_i sum_j |a_ij| / |a_ii| as the bit pattern of a non-negative double
+  int keep_km;                     // also store K and M
+  int same;                        // both fields carry the same Dirichlet set (one mask gather per entry)
+  // ld > 0: A11 .. A21 are stencil-ELL arrays (pph_sell.hip): entry (row, column row + (dx,dy,dz)) is stored at
+  // [slot_of[(dz+1)*9 + (dy+1)*3 + (dx+1)] * ld + row]; ld == 0: CSR value arrays addressed by the pattern position
+  // With symmetric storage (Sell::sym) only the diagonal and the upper slots are stored: slot_of is then the STORED
+  // slot (s - S/2) or -1 for a lower slot, whose entry is not written.  The diagonal blocks (slot_of) and the coupling
+  // blocks (slot_of_c: symmetric only when both fields carry the same Dirichlet set) have their own tables.
+  int symg;                        // symmetric storage on a slab: ghost rows keep their entries towards owned columns
+  int64_t ld;
+  int8_t slot_of[27];
+  int8_t slot_of_c[27];
+  // k_asm_node2 on a uniform box (MeshData::uniform): the canonical edge lengths the cells are integrated on
+  double hcan[3] = {0, 0, 0};
+  // k_asm_node2, listed mode: row i of the (mini) output is the row of node list[i]
+  const uint32_t* list = nullptr;
+  // k_asm_node2, check mode (row dictionaries, pph_sell.hip "check fused into the assembly"): class arrays, tables and status
+  // words of the operators this launch writes (0: A11, 1: A22, 2: A12; null: no dictionary), the alarm word of the context
+  const uint16_t* dcls[3] = {nullptr, nullptr, nullptr};
+  const double* dtab[3] = {nullptr, nullptr, nullptr};
+  int* dstate[3] = {nullptr, nullptr, nullptr};
+  int dn[3] = {0, 0, 0};
+  int* alarm = nullptr;
+  int guard = 0;                   // k_asm_node2 MODE 5: 1 = return at once unless one of dstate[d][1] is negative
+  // k_asm_node2 in two launches, k_n2_check_general: the wave map that follows the grid lines (WaveMap; n2_wave).  Null: a
+  // wave is 64 consecutive aligned rows
+  const uint32_t* wm_win = nullptr;
+  const uint32_t* wm_pairs = nullptr;
+  int wm_nwin = 0, wm_ngen = 0;
+  // host side only: that map's owner (built on first use); the group and dictionaries behind the check, and the views they describe
+  WaveMap* wm = nullptr;
+  DictGroup* G = nullptr;
+  SellDict* dicts[3] = {nullptr, nullptr, nullptr};
+  const Sell* views[3] = {nullptr, nullptr, nullptr};
+  ValuesState* vs = nullptr;       // the level's record of what this assembly leaves in A11 .. A21 (null: none kept)
+};
+// What the stored operator values of a level hold (option asm_store_values 0, single context).  An assembly whose straight-line
+// rows are checked against the row dictionaries does not store them: no product reads them while the dictionaries stand.
+// `stale`: the window rows of A11 .. A21 were not written by the last assembly; `last` (that assembly's launch arguments:
+// coefficients, canonical edges, wave map, storage) is what sell_values_ensure needs to write them now, bit for bit.
+// `base`: the arrays a storing assembly last wrote completely - only such arrays may be left unwritten.
+struct ValuesState {
+  bool stale = false;
+  FuseArgs last;
+  int variant = -1;
+  bool uni = false;
+  const double* base[4] = {nullptr, nullptr, nullptr, nullptr};
+};
+
 // stencil of a cell kind as (dy,dz) lines with a 3-bit mask of the dx in {-1,0,+1} present, lines in ascending
 // (dz,dy) order: slot numbering = ascending (dz,dy,dx) = the CSR column order (make_stencil)
 template <int KIND> struct SellSt;
@@ -265,6 +326,7 @@ struct MgLevel {
   DevBuf<uint8_t> mask[2];       // per field: non-zero where the dof is constrained
   DevBuf<uint8_t> rownear;       // rows that need the masks (fused level operators); follows the masks
   WaveMap wmap;                  // wave map of the node assembly kernel on this level; follows rownear
+  ValuesState vals;              // what own_ell holds after the last assembly (levels >= 1; level 0: pph_ctx::vals0)
   DevBuf<uint8_t> rfast[2];     // per field: coarse nodes whose 3^d fine neighbours are all inside, owned and unconstrained (restriction fast path)
   int bc_epoch = -1;             // ctx->bc_epoch the masks / rownear were derived from
   const uint8_t* maskp[2] = {nullptr, nullptr};
@@ -374,6 +436,11 @@ struct pph_ctx {
   Sell S11, S22, S12, S21;              // views of E* (S21 == S12 when a21_alias)
   SellDict D11, D22, D12;               // their row dictionaries (sell_dict; S21 shares D12 when aliased, else none)
   DictGroup DG;                         // fused-check group of the three
+  ValuesState vals0;                    // what E11 .. E21 hold after the last assembly (operator values on demand)
+  int asm_store_values = 0;             // option "asm_store_values": 1 = every assembly stores every operator entry; 0 = a check-mode assembly leaves the straight-line rows to sell_values_ensure
+  int values_peek = 0;                  // option "asm_values_peek" (test aid): sell_values_ensure does nothing
+  int64_t n_values_materialized = 0;    // sell_values_ensure launches since the context was created (pph_get_timers out[33])
+  int64_t n_store_repairs = 0;          // levels whose refusal on the device sell_dict_poll met while their values were marked stale (out[34])
   int dict_fuse = 1;                    // option "sell_dict_fuse": the per-assembly check of every row runs inside the assembly kernel (0: k_dict_verify_sym)
   bool ell_ok = false;                  // S* hold the assembled blocks
   bool csr_ok = false;                  // A11 .. A21 hold the assembled blocks
@@ -539,7 +606,11 @@ int pph_launch_level_operators(pph_ctx* ctx, MeshData& mesh, const uint8_t* m1, 
                                int same, double coefK1, double coefK2, double coefM, double* A1, double* A2,
                                double* dinv1, double* dinv2, unsigned long long* lam, int64_t ell_ld, int ell_sym,
                                DictGroup* group = nullptr, SellDict* dicts = nullptr, const Sell* views = nullptr,
-                               WaveMap* wmap = nullptr);
+                               WaveMap* wmap = nullptr, ValuesState* vstate = nullptr);
+// stored operator values on demand (ValuesState; pph_assemble.hip): writes the rows the last assembly of `level` left out
+// (level < 0: of every level) / of the level that `val` is an operator array of; no-ops when nothing is stale
+int sell_values_ensure(pph_ctx* ctx, int level);
+int sell_values_ensure_for(pph_ctx* ctx, const double* val);
 void pph_launch_row_near(pph_ctx* ctx, const MeshData& mesh, const uint8_t* m1, const uint8_t* m2, uint8_t* out);   // (stencil walk: no CSR pattern)
 
 // linear algebra on the context stream; all results that feed control flow go through ctx->scal

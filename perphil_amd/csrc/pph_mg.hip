@@ -492,6 +492,7 @@ void mg_release(pph_ctx* ctx) {
     }
     L.x.release(); L.b.release(); L.r.release(); L.d.release(); L.t.release(); L.w.release();
     L.wmap.release();
+    L.vals = ValuesState();
   }
   ctx->mg.clear();
   ctx->mg_w.release();
@@ -645,7 +646,9 @@ int mg_setup(pph_ctx* ctx) {
         L.maskp[f] = L.mask[f].p;
         L.ell[f] = Sell();
         if (ell_only) {
+          const double* const was = L.own_ell[f].p;
           PPH_TRY(sell_alloc(ctx, m, L.own_ell[f], &L.ell[f], pph_sell_sym(ctx)));
+          if (was != L.own_ell[f].p) L.vals = ValuesState();   // (allocated anew: what was known about the old array goes with it)
           L.val[f] = nullptr;
         } else {
           PPH_TRY(L.own_val[f].alloc(ctx, (size_t)L.nnz));
@@ -664,7 +667,7 @@ int mg_setup(pph_ctx* ctx) {
                                            ell_only ? L.own_ell[1].p : L.own_val[1].p, L.dinv[0].p, L.dinv[1].p,
                                            lamdev.p + 2 * l, ell_only ? L.ell[0].ld : 0, ell_only ? L.ell[0].sym : 0,
                                            ell_only ? &L.dgroup : nullptr, ell_only ? L.dict : nullptr, ell_only ? L.ell : nullptr,
-                                           &L.wmap));
+                                           &L.wmap, ell_only ? &L.vals : nullptr));
         level_fused = true;
         if (ell_only) {
           const int b0 = ctx->n_dict_build;
@@ -679,6 +682,7 @@ int mg_setup(pph_ctx* ctx) {
         for (int f = 0; f < 2; ++f) {
           pph_launch_scalar_block(ctx, m, L.maskp[f], coefK[f], ctx->b, L.own_val[f].p);
           if (use_ell) PPH_TRY(sell_from_csr(ctx, m, L.own_val[f].p, L.own_ell[f], &L.ell[f], pph_sell_sym_from_csr(ctx)));
+          L.vals = ValuesState();   // (written completely, by another path)
         }
       }
       L.bc_epoch = ctx->bc_epoch;
@@ -943,6 +947,7 @@ __global__ __launch_bounds__(1024) void k_coarse_cg_sell(const double* __restric
 
 void mg_onchip_cg(pph_ctx* ctx, const Sell& E, const double* dinv, const double* b, double* x, double* r, double* p, double* q,
                   int64_t n, double rtol, int max_it, unsigned long long* rec) {
+  (void)sell_values_ensure_for(ctx, E.val);   // (reads the stored values, dictionary or not)
   hipLaunchKernelGGL(k_coarse_cg_sell, dim3(1), dim3(n <= 256 ? 256 : 1024), 0, ctx->stream, E.val, E.ld, E.sym, make_stencil(E.kind),
                      E.px, E.py, E.pz, dinv, b, x, r, p, q, (int)n, rtol, max_it, rec);
 }
@@ -1381,6 +1386,7 @@ static int mg_tail_pack(pph_ctx* ctx, int which) {
   for (int q = 0; q < pa.nl; ++q) {
     MgLevel& L = mg[lt + q];
     TailSrc& T = pa.L[q];
+    PPH_TRY(sell_values_ensure_for(ctx, L.ell[which].val));   // (the pack copies the stored values, dictionary or not)
     T.A = L.ell[which].val; T.sym = L.ell[which].sym; T.ld = L.ell[which].ld; T.dinv = L.dinv[which].p; T.mask = L.maskp[which];
     T.px = L.px; T.py = L.py; T.pz = L.pz; T.n = (int)L.n;
     ns[q] = (int)L.n;
@@ -1501,6 +1507,7 @@ static void mg_vcycle_fused(pph_ctx* ctx, int which, const double* rin, double* 
     MgLevel& C = mg[nlev - 1];
     int its = 0;
     ctx->comm_suspended = C.replicated;
+    (void)sell_values_ensure_for(ctx, C.ell[which].val);
     if ((!dist || C.replicated) && C.n <= 4096 && ctx->coarse_on_device)
       hipLaunchKernelGGL(k_coarse_cg_sell, dim3(1), dim3(C.n <= 256 ? 256 : 1024), 0, ctx->stream, C.ell[which].val,
                          C.ell[which].ld, C.ell[which].sym, make_stencil(kind), C.px, C.py, C.pz, C.dinv[which].p, C.b.p, C.x.p, C.r.p,
@@ -1603,6 +1610,7 @@ void mg_vcycle(pph_ctx* ctx, int which, const double* rin, double* zout, int nsm
     MgLevel& C = mg[nlev - 1];
     int its = 0;
     ctx->comm_suspended = C.replicated;
+    (void)sell_values_ensure_for(ctx, C.ell[which].val);
     if ((!dist || C.replicated) && C.n <= 4096 && ctx->coarse_on_device && C.ell[which].val)
       hipLaunchKernelGGL(k_coarse_cg_sell, dim3(1), dim3(C.n <= 256 ? 256 : 1024), 0, ctx->stream, C.ell[which].val,
                          C.ell[which].ld, C.ell[which].sym, make_stencil(ctx->mesh.kind), C.px, C.py, C.pz, C.dinv[which].p, C.b.p, C.x.p,

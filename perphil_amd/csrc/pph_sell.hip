@@ -723,6 +723,9 @@ int sell_spmv(pph_ctx* ctx, const Sell& E, int64_t n, int mode, const double* x,
   // profiles/r02_sell_sym_probe_256.txt, r02_sell_sym_probe2_256.txt)
   const bool zw = E.sym && E.pz > 2 && ctx->sell_zwalk > 0 && chunk0 == 0 && nchunks >= ctx->sell_zwalk_min_chunks;   // (smaller levels: too few chunks per workgroup)
   const bool dict = rpt == 2 && E.sym && E.dict && E.dict->on;
+  // (a plain product reads the stored values: whole before it runs, ValuesState; status ignored here as for the launches below -
+  // a failed launch surfaces at the caller's next check of the stream)
+  if (!dict) (void)sell_values_ensure_for(ctx, E.val);
   if (dict && cend < 0) {
     const int g = sell_launch_dict_walk(ctx, mode, E, x, b, dinv, w, y, aux, z0, n, part, dlo, dhi);
     if (g > 0) return g;
@@ -985,6 +988,7 @@ int sell_dict_update(pph_ctx* ctx, Sell* E, SellDict& D, int64_t n) {
     E->dict = &D;
     return PPH_OK;
   }
+  PPH_TRY(sell_values_ensure_for(ctx, E->val));   // (table, check and build below read the stored values)
   if (same && D.on) {
     // re-assembly: same classes expected - re-read the table from the representatives, check every row
     hipLaunchKernelGGL(k_dict_table, dim3(1), dim3(256), 0, ctx->stream, E->val, E->ld, E->sym, st, E->px, pxy, n, D.keys.p,
@@ -1193,6 +1197,9 @@ int dict_group_tables(pph_ctx* ctx, DictGroup& G, SellDict* const* dicts, int nd
 int sell_dict_poll(pph_ctx* ctx) {
   if (!ctx->dict_alarm || !*ctx->dict_alarm) return PPH_OK;
   *ctx->dict_alarm = 0;
+  // A level whose values were marked stale when its dictionary was refused: the guarded launch behind that assembly's last check
+  // kernel saw the same status word and has written the rows (pph_assemble.hip: n2_launch_values) - the mark goes.
+  auto repaired = [&](ValuesState& V) { if (V.stale) { V.stale = false; ctx->n_store_repairs++; } };
   auto retire = [&](Sell& E, SellDict& D) -> int {
     if (!D.on || !D.state.p) return PPH_OK;
     int h[2] = {0, 0};
@@ -1207,12 +1214,14 @@ int sell_dict_poll(pph_ctx* ctx) {
   if ((r = retire(ctx->S11, ctx->D11)) < 0) return r; n += r;
   if ((r = retire(ctx->S22, ctx->D22)) < 0) return r; n += r;
   if ((r = retire(ctx->S12, ctx->D12)) < 0) return r; n += r;
+  if (n) repaired(ctx->vals0);
   if (ctx->S21.dict && !ctx->D12.on) ctx->S21.dict = nullptr;
   for (size_t l = 0; l < ctx->mg.size(); ++l)
     for (int f = 0; f < 2; ++f) {
       MgLevel& L = ctx->mg[l];
       if (l == 0) { if (L.ell[f].dict && !L.ell[f].dict->on) L.ell[f].dict = nullptr; continue; }   // level 0 aliases S11 / S22
       if ((r = retire(L.ell[f], L.dict[f])) < 0) return r; n += r;
+      if (r) repaired(L.vals);
     }
   if (n) la_release_graphs(ctx);   // captured launches carry the dictionary kernels
   return PPH_OK;
@@ -1280,6 +1289,7 @@ int sell_from_csr(pph_ctx* ctx, const MeshData& mesh, const double* csr_val, Dev
 }
 
 int sell_to_csr(pph_ctx* ctx, const MeshData& mesh, const Sell& E, double* csr_val) {
+  PPH_TRY(sell_values_ensure_for(ctx, E.val));
   hipLaunchKernelGGL(k_sell_convert<false>, dim3(sell_grid(mesh.n)), dim3(256), 0, ctx->stream, mesh.rowptr.p, csr_val,
                      const_cast<double*>(E.val), E.ld, make_stencil(mesh.kind), mesh.px, mesh.py, mesh.pzl, mesh.n, E.sym,
                      mesh.glo ? 1 : 0, mesh.ghi ? 1 : 0);
