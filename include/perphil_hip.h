@@ -231,6 +231,36 @@ int pph_bw_probe(pph_ctx* ctx, int64_t bytes, int mode, int blocks, double* ms_o
  * pairs may be null (sizes only), else they hold at least that many entries. */
 int pph_asm_wave_map(int dim, int px, int py, int pz, int align, const uint8_t* near, uint32_t* win, uint32_t* pairs, int64_t* counts);
 
+/* ---- extreme eigenvalues / condition numbers on the device -------------------------------------------
+ * replaces: calculate_condition_number() of the exported matrix (reference src/perphil/solvers/conditioning.py:105-218)
+ * for the symmetric positive definite operators: kappa = lambda_max / lambda_min without the matrix leaving the device.
+ *
+ * extreme eigenvalues of a symmetric operator of the context, plain Lanczos on the device (no reorthogonalisation).
+ * which: 0 monolithic (needs monolithic assembly), 2 M, 3 A11, 4 A22 (pph_get_csr's selectors; anything else,
+ * or world != 1: PPH_ERR_INVALID with a message).  Works on degree-1 and degree-2 contexts; the product is the one pph_spmv
+ * would run (stencil-ELL copy or row dictionary for the CG-1 blocks, CSR for the monolithic system and degree 2).
+ * tol <= 0: 1e-10; max_it <= 0: 20 000; check_every <= 0: 32.  Start vector: a fixed hash of the row index, normalised.
+ * Every check_every steps the host reads the recurrence coefficients (one synchronisation) and takes the extremes theta of the
+ * tridiagonal matrix T they form; an end is converged when |beta_m s_m| <= tol |theta| (s_m: last component of T's normalised
+ * eigenvector) and stays converged.  Breakdown: the first j with beta_j not finite or <= 1e-13 max(|alpha_i|, beta_0) ends the
+ * recurrence on an invariant subspace; the extremes of T's leading j + 1 rows are then exact.
+ * out[0] lambda_min, out[1] lambda_max, out[2] Lanczos steps taken, out[3] 1 converged / 0 stopped at max_it (values still
+ * returned), out[4] 1 when the recurrence ended on an invariant subspace (breakdown), out[5], out[6] the final estimates
+ * |beta_m s_m| of the two ends (0 after a breakdown), out[7] ms on the device (event pair), out[12] rows of the T the values
+ * were taken from (= out[2], or j + 1 after a breakdown).
+ * vec_lo / vec_hi: NULL, or caller-owned DEVICE arrays of nrows doubles that receive the normalised Ritz vectors (a second
+ * pass of the same recurrence accumulates them; the context stream has finished with them on return); then out[8], out[9] =
+ * their Rayleigh quotients, out[10], out[11] = ||A y - rq y||_2.  A plain-Lanczos Ritz vector's residual is NOT bounded by
+ * tol: it is reported, not promised.
+ * fp64, no floating-point atomics: two calls give the same bits.  Memory: 3 vectors of nrows (5 with Ritz vectors) and
+ * 2 max_it doubles, released on return. */
+int pph_extreme_eigenvalues(pph_ctx* ctx, int which, double tol, int max_it, int check_every,
+                            double* vec_lo, double* vec_hi, double* out /* [13], host */);
+/* host only, no device touched (like pph_asm_wave_map): smallest and largest eigenvalue of the symmetric
+ * tridiagonal (alpha[0..m), beta[0..m-1)) by Sturm bisection and the LAST component of their normalised eigenvectors (inverse
+ * iteration); out4 = {theta_min, theta_max, s_min_last, s_max_last} */
+int pph_tridiag_extremes(const double* alpha, const double* beta, int m, double* out4);
+
 /* ---- error norms (post-processing) -----------------------------------------------------------------
  * replaces: l2_error() / h1_seminorm_error() (reference src/perphil/utils/postprocessing.py:89-124) for
  * the manufactured pressures of src/perphil/utils/manufactured_solutions.py:39-51 (2D), :87-88 (3D).

@@ -43,6 +43,7 @@ EXPORTS = [
     "pph_eval_points", "pph_eval_points_device",
     "pph_integrate", "pph_integrate_device", "pph_boundary_flux", "pph_boundary_flux_device",
     "pph_dpp_nodal_flux", "pph_dpp_nodal_flux_device",
+    "pph_extreme_eigenvalues", "pph_tridiag_extremes",
 ]
 
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64)
@@ -192,6 +193,8 @@ def _load() -> C.CDLL:
         "pph_boundary_flux_device": ([p, C.c_void_p, C.c_double, f64p], C.c_int),
         "pph_dpp_nodal_flux": ([p] + [C.c_double] * 4 + [C.c_void_p, C.c_void_p], C.c_int),
         "pph_dpp_nodal_flux_device": ([p] + [C.c_double] * 4 + [C.c_void_p, C.c_void_p], C.c_int),
+        "pph_extreme_eigenvalues": ([p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, f64p], C.c_int),
+        "pph_tridiag_extremes": ([C.c_void_p, C.c_void_p, C.c_int, f64p], C.c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = ABI mismatch: fail loudly
@@ -201,6 +204,20 @@ def _load() -> C.CDLL:
 
 
 lib = _load()
+
+
+def tridiag_extremes(alpha, beta) -> tuple:
+    """(theta_min, theta_max, last component of either normalised eigenvector) of the symmetric tridiagonal matrix with
+    diagonal `alpha` [m] and off-diagonal `beta` [m - 1]: the host routine behind the Lanczos checks (no device touched)."""
+    alpha = np.ascontiguousarray(alpha, dtype=np.float64)
+    beta = np.ascontiguousarray(beta, dtype=np.float64)
+    if alpha.ndim != 1 or alpha.size < 1 or beta.shape != (alpha.size - 1,):
+        raise ValueError("tridiag_extremes: alpha [m >= 1] and beta [m - 1]")
+    out = (C.c_double * 4)()
+    st = lib.pph_tridiag_extremes(_ptr(alpha), _ptr(beta) if beta.size else None, int(alpha.size), out)
+    if st != PPH_OK:
+        raise ValueError((lib.pph_last_error(None) or b"").decode())
+    return out[0], out[1], out[2], out[3]
 
 
 class ConvergenceError(RuntimeError):
@@ -655,6 +672,31 @@ class Context:
         self._check(lib.pph_pc_bench(self._h, int(which), int(pc_type), int(mg_smooth), int(reps),
                                      out.ctypes.data_as(C.POINTER(C.c_double))))
         return {"apply_ms": out[0], "level0_ms": out[1], "level0_bytes": out[2], "setup_ms": out[3]}
+
+    def extreme_eigenvalues(self, which: int, tol: float = 1e-10, max_it: int = 20000, check_every: int = 32,
+                            vectors: bool = False) -> dict:
+        """lambda_min and lambda_max of a symmetric operator of the context (MAT_MONO, MAT_M, MAT_A11, MAT_A22) by plain
+        Lanczos on the device (pph_extreme_eigenvalues): nothing but the recurrence coefficients reaches the host.  Returns
+        the fields of its `out`; `converged` 0 means stopped at max_it (values still returned).  vectors=True: also the two
+        normalised Ritz vectors as device tensors (`vector_min`, `vector_max`), their Rayleigh quotients and true residual
+        norms ||A y - rq y||."""
+        out = np.zeros(13, dtype=np.float64)
+        ylo = yhi = None
+        if vectors:
+            require_shared_runtime("extreme_eigenvalues(vectors=True)")
+            nrows = 2 * self.n if int(which) == MAT_MONO else self.n
+            ylo, yhi = self._device_out(nrows), self._device_out(nrows)
+        self._check(lib.pph_extreme_eigenvalues(self._h, int(which), float(tol), int(max_it), int(check_every),
+                                                _tptr(ylo) if vectors else None, _tptr(yhi) if vectors else None,
+                                                out.ctypes.data_as(C.POINTER(C.c_double))))
+        res = {"lambda_min": float(out[0]), "lambda_max": float(out[1]), "iterations": int(out[2]), "converged": int(out[3]),
+               "breakdown": int(out[4]), "estimate_min": float(out[5]), "estimate_max": float(out[6]),
+               "device_ms": float(out[7]), "krylov_dimension": int(out[12])}
+        if vectors:
+            self.torch_waits()
+            res.update(vector_min=ylo, vector_max=yhi, rayleigh_min=float(out[8]), rayleigh_max=float(out[9]),
+                       residual_min=float(out[10]), residual_max=float(out[11]))
+        return res
 
     def spmv_bench(self, which: int, reps: int) -> float:
         ms = C.c_double()

@@ -47,6 +47,17 @@ def _context(space):
 
 def get_matrix_data_from_form(form, boundary_conditions: List[fd.DirichletBC], symmetry_tolerance: float = 1e-8) -> MatrixData:
     """Assemble `form` (monolithic DPP form or one Picard block) with the BCs and export it as SciPy CSR."""
+    ctx, which = _assemble_for(form, boundary_conditions)
+    csr = ctx.csr(which)
+    csr = csr_matrix(csr)
+    csr.eliminate_zeros()
+    asym = abs(csr - csr.T)
+    is_symmetric = bool((asym.max() if asym.nnz else 0.0) <= symmetry_tolerance)
+    return MatrixData(is_symmetric, csr, int(csr.nnz), int(csr.shape[0]), symmetry_tolerance)
+
+
+def _assemble_for(form, boundary_conditions: List[fd.DirichletBC]):
+    """Assembles `form` on its mesh's context as get_matrix_data_from_form does; returns (context, matrix selector)."""
     if form.space.mesh().distributed:
         raise NotImplementedError("matrix export is an analysis path on the whole matrix: build the mesh with "
                                   "comm=fd.COMM_SELF under torch.distributed")
@@ -54,22 +65,36 @@ def get_matrix_data_from_form(form, boundary_conditions: List[fd.DirichletBC], s
         ctx = _context(form.space)
         _set_bcs(ctx, form.space, boundary_conditions)
         ctx.assemble(form.k1, form.k2, form.beta, form.mu, monolithic=True)
-        csr = ctx.csr(_ffi.MAT_MONO)
-    elif isinstance(form, ScalarBlockForm) and form.rank == 2:
+        return ctx, _ffi.MAT_MONO
+    if isinstance(form, ScalarBlockForm) and form.rank == 2:
         ctx = _context(form.space)
         # a scalar block (coef_K K + coef_M M): assemble the pair with the block's coefficients on its own field
         bcs = [fd.DirichletBC(_as_field(bc, form.field), bc.value, bc.sub_domain) for bc in boundary_conditions or []]
         _set_bcs(ctx, form.space, bcs)
         k = form.coef_K if form.coef_K > 0 else 1.0
         ctx.assemble(k, k, form.coef_M, 1.0, monolithic=False)
-        csr = ctx.csr(_ffi.MAT_A11 if form.field == 0 else _ffi.MAT_A22)
-    else:
-        raise TypeError(f"cannot assemble {type(form)}")
-    csr = csr_matrix(csr)
-    csr.eliminate_zeros()
-    asym = abs(csr - csr.T)
-    is_symmetric = bool((asym.max() if asym.nnz else 0.0) <= symmetry_tolerance)
-    return MatrixData(is_symmetric, csr, int(csr.nnz), int(csr.shape[0]), symmetry_tolerance)
+        return ctx, (_ffi.MAT_A11 if form.field == 0 else _ffi.MAT_A22)
+    raise TypeError(f"cannot assemble {type(form)}")
+
+
+def _kappa_on_device(ctx, which: int, tol: float, zero_tol: float) -> float:
+    r = ctx.extreme_eigenvalues(which, tol=tol)
+    if not r["converged"]:
+        raise RuntimeError(f"Lanczos did not converge in {r['iterations']} steps: lambda_min {r['lambda_min']:.6e} "
+                           f"(estimate {r['estimate_min']:.1e}), lambda_max {r['lambda_max']:.6e} (estimate {r['estimate_max']:.1e})")
+    if r["lambda_min"] <= zero_tol:
+        return float("inf")
+    return float(r["lambda_max"] / r["lambda_min"])
+
+
+def condition_number_on_device(form, boundary_conditions: List[fd.DirichletBC], tol: float = 1e-10,
+                               zero_tol: float = DEFAULT_CONDITION_NUMBER_TOLERANCE) -> float:
+    """kappa = lambda_max / lambda_min of the assembled `form` (the forms get_matrix_data_from_form accepts: symmetric
+    positive definite after the symmetric Dirichlet elimination, so singular values are eigenvalues) by Lanczos on the
+    device: assembled like get_matrix_data_from_form, nothing exported.  inf when lambda_min does not exceed `zero_tol`
+    (the reference's sparse branch, conditioning.py:204-209); RuntimeError when the iteration did not converge."""
+    ctx, which = _assemble_for(form, boundary_conditions)
+    return _kappa_on_device(ctx, which, tol, zero_tol)
 
 
 class _FieldView(fd.FunctionSpace):

@@ -555,6 +555,23 @@ int pph_spmv(pph_ctx* ctx, int which, const double* x_host, double* y_host) {
   return PPH_OK;
 }
 
+int pph_extreme_eigenvalues(pph_ctx* ctx, int which, double tol, int max_it, int check_every, double* vec_lo, double* vec_hi,
+                            double* out) {
+  if (!ctx) return PPH_ERR_INVALID;
+  PPH_REQUIRE(ctx, out != nullptr, "out is NULL");
+  PPH_REQUIRE(ctx, ctx->world == 1, "pph_extreme_eigenvalues works on a single context (the whole operator on one device)");
+  PPH_REQUIRE(ctx, which == 0 || (which >= 2 && which <= 4),
+              "pph_extreme_eigenvalues: which must be 0 (monolithic), 2 (M), 3 (A11) or 4 (A22), the symmetric positive "
+              "definite operators; got %d", which);
+  PPH_HIP(ctx, hipSetDevice(ctx->device));
+  Csr A;   // the operator format pph_spmv would run this product on
+  if (!select_sell_only(ctx, which, &A)) {
+    PPH_TRY(select_csr(ctx, which, &A));
+    PPH_TRY(attach_sell(ctx, which, &A));
+  }
+  return pph_eig_lanczos(ctx, A, tol, max_it, check_every, vec_lo, vec_hi, out);
+}
+
 __global__ void k_fill_pattern(double* __restrict__ x, int64_t n) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     // cheap deterministic pseudo-random values in (-1, 1)

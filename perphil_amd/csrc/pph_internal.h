@@ -758,6 +758,9 @@ bool mg_pre_smoother(pph_ctx* ctx, int which, int nsmooth, const double** dinv, 
                      bool* launch_only);
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// extreme eigenvalues of a symmetric operator by plain Lanczos (pph_eig.hip; out as pph_extreme_eigenvalues documents it)
+int pph_eig_lanczos(pph_ctx* ctx, const Csr& A, double tol, int max_it, int check_every, double* vec_lo, double* vec_hi,
+                    double* out);
 // p-multigrid (pph_pmg.hip): the passes over the degree-2 level of a PPH_PC_PMG cycle
 bool pmg_level0_ok(const pph_ctx* ctx, const Csr& A);   // the tile kernels serve this operator (else: the generic composition)
 // t = A d; r -= t; dnew = c1 d + c2 dinv r; x += dnew   (one Chebyshev-Jacobi step; dnew != d)

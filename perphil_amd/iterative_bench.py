@@ -109,7 +109,21 @@ def assemble_monolithic_matrix(W, params: Optional[DPPParameters] = None,
 
 
 def estimate_condition_numbers(W, params: Optional[DPPParameters] = None, bcs: Optional[List[fd.DirichletBC]] = None,
-                               num_of_factors: Optional[int] = 50, use_sparse: bool = True) -> Dict[str, float]:
+                               num_of_factors: Optional[int] = 50, use_sparse: bool = True, on_device: bool = False,
+                               tol: float = 1e-10) -> Dict[str, float]:
+    """kappa of the monolithic system and of its two diagonal blocks.  on_device: one monolithic assembly, then the extreme
+    eigenvalues of the three operators by Lanczos on the same context (conditioning.condition_number_on_device's rules) -
+    no matrix leaves the device; `num_of_factors` and `use_sparse` belong to the host path and are not used."""
+    if on_device:
+        from . import _ffi
+
+        params = params or default_model_params()
+        bcs = bcs or default_bcs(W)
+        a, _L = dpp_form(W, params)
+        ctx, _which = conditioning._assemble_for(a, bcs)
+        zt = conditioning.DEFAULT_CONDITION_NUMBER_TOLERANCE
+        return {name: conditioning._kappa_on_device(ctx, which, tol, zt)
+                for name, which in (("monolithic", _ffi.MAT_MONO), ("macro", _ffi.MAT_A11), ("micro", _ffi.MAT_A22))}
     csr, n0, n1 = assemble_monolithic_matrix(W, params=params, bcs=bcs)
     cond = conditioning.calculate_condition_number
     kw = {"num_singular_values": num_of_factors, "use_sparse": use_sparse}
