@@ -256,6 +256,34 @@ int pph_asm_wave_map(int dim, int px, int py, int pz, int align, const uint8_t* 
  * 2 max_it doubles, released on return. */
 int pph_extreme_eigenvalues(pph_ctx* ctx, int which, double tol, int max_it, int check_every,
                             double* vec_lo, double* vec_hi, double* out /* [13], host */);
+/* extreme eigenvalues of the PRECONDITIONED operator B A: what a Krylov method under one of the library's symmetric
+ * preconditioners sees (kappa(B A) = out[1] / out[0]), without A or B leaving the device (no reference counterpart: the
+ * reference's studies stop at the unpreconditioned operators).  Lanczos for the pencil (A, B^-1) in the B inner product: two
+ * sequences u_j and v_j = B u_j, one product and one preconditioner application per step, B^-1 never applied, no
+ * reorthogonalisation.
+ * which / pc_type (everything else, or world != 1: PPH_ERR_INVALID with a message):
+ *   3 (A11), 4 (A22): PPH_PC_JACOBI, PPH_PC_ILU, PPH_PC_MG (degree-1 contexts only), PPH_PC_PMG (at degree 1 it is PPH_PC_MG);
+ *   0 (monolithic, needs monolithic assembly): PPH_PC_JACOBI, PPH_PC_BLOCK2, PPH_PC_ILU;
+ *   2 (M): PPH_PC_JACOBI.
+ * PPH_PC_NONE is refused (that is pph_extreme_eigenvalues), PPH_PC_FIELDSPLIT as well (the multiplicative split is not
+ * symmetric).  mg_smooth as in pph_solver_cfg (<= 0: 2).
+ * Constrained rows: the iteration runs on the FREE rows only - the start vector (the hash of pph_extreme_eigenvalues) is set to
+ * 0 on the rows of the block's Dirichlet mask (monolithic: of both fields' masks) and B's result is 0 there - because that is the
+ * operator the Krylov loops see: their residuals are 0 on constrained rows.  pph_extreme_eigenvalues, in contrast, counts the
+ * unit rows (an eigenvalue 1 per constrained row).  No free row: PPH_ERR_INVALID ("no free rows").
+ * tol <= 0: 1e-4; max_it <= 0: 2000; check_every <= 0: 16 - not the defaults of pph_extreme_eigenvalues: under multigrid the
+ * eigenvalues of B A pile up at the upper end, where the Ritz residual shrinks far more slowly than the Ritz value moves
+ * ("Preconditioned extremes").  Stopping and breakdown rules: those of pph_extreme_eigenvalues.
+ * Positive definiteness: r.Br below -1e-13 max(|alpha_i|, beta_0)^2 at a step, or a negative u.Bu of the start vector, means
+ * that B is not positive definite on the Krylov space: PPH_ERR_INVALID with a message, not a breakdown.
+ * out[0] lambda_min, out[1] lambda_max of B A on the free rows, out[2] steps taken, out[3] 1 converged / 0 stopped at max_it
+ * (values still returned), out[4] 1 after a breakdown, out[5], out[6] the final estimates |beta_m s_m| of the two ends (0 after
+ * a breakdown), out[7] ms on the device (event pair, set-up excluded), out[8] rows of the T the values were taken from,
+ * out[9] ms of the preconditioner's set-up (hierarchy or factorisation; 0 when it was up to date).
+ * fp64, no floating-point atomics: two calls give the same bits.  Memory: 5 vectors of nrows and 3 max_it doubles (device and
+ * pinned) plus what the preconditioner owns; the call's own buffers are released on return. */
+int pph_preconditioned_extremes(pph_ctx* ctx, int which, int pc_type, int mg_smooth, double tol, int max_it, int check_every,
+                                double* out /* [10], host */);
 /* host only, no device touched (like pph_asm_wave_map): smallest and largest eigenvalue of the symmetric
  * tridiagonal (alpha[0..m), beta[0..m-1)) by Sturm bisection and the LAST component of their normalised eigenvectors (inverse
  * iteration); out4 = {theta_min, theta_max, s_min_last, s_max_last} */

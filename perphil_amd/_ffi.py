@@ -43,7 +43,7 @@ EXPORTS = [
     "pph_eval_points", "pph_eval_points_device",
     "pph_integrate", "pph_integrate_device", "pph_boundary_flux", "pph_boundary_flux_device",
     "pph_dpp_nodal_flux", "pph_dpp_nodal_flux_device",
-    "pph_extreme_eigenvalues", "pph_tridiag_extremes",
+    "pph_extreme_eigenvalues", "pph_tridiag_extremes", "pph_preconditioned_extremes",
 ]
 
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64)
@@ -195,6 +195,7 @@ def _load() -> C.CDLL:
         "pph_dpp_nodal_flux_device": ([p] + [C.c_double] * 4 + [C.c_void_p, C.c_void_p], C.c_int),
         "pph_extreme_eigenvalues": ([p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, f64p], C.c_int),
         "pph_tridiag_extremes": ([C.c_void_p, C.c_void_p, C.c_int, f64p], C.c_int),
+        "pph_preconditioned_extremes": ([p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, f64p], C.c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = ABI mismatch: fail loudly
@@ -697,6 +698,22 @@ class Context:
             res.update(vector_min=ylo, vector_max=yhi, rayleigh_min=float(out[8]), rayleigh_max=float(out[9]),
                        residual_min=float(out[10]), residual_max=float(out[11]))
         return res
+
+    def preconditioned_extremes(self, which: int, pc_type: int, mg_smooth: int = 2, tol: float = 1e-4, max_it: int = 2000,
+                                check_every: int = 16) -> dict:
+        """lambda_min and lambda_max of B A on the free rows - A the operator `which` (MAT_MONO, MAT_M, MAT_A11, MAT_A22), B
+        the symmetric preconditioner `pc_type` (blocks: PC_JACOBI, PC_ILU, PC_MG, PC_PMG; monolithic: PC_JACOBI, PC_BLOCK2,
+        PC_ILU; M: PC_JACOBI) - by Lanczos in the B inner product on the device (pph_preconditioned_extremes).  Returns the
+        keys of extreme_eigenvalues plus `setup_ms` (the preconditioner's set-up, 0 when it was up to date) and `kappa` =
+        lambda_max / lambda_min (inf when lambda_min is not positive); `converged` 0 means stopped at max_it."""
+        out = np.zeros(10, dtype=np.float64)
+        self._check(lib.pph_preconditioned_extremes(self._h, int(which), int(pc_type), int(mg_smooth), float(tol), int(max_it),
+                                                    int(check_every), out.ctypes.data_as(C.POINTER(C.c_double))))
+        lo, hi = float(out[0]), float(out[1])
+        return {"lambda_min": lo, "lambda_max": hi, "iterations": int(out[2]), "converged": int(out[3]),
+                "breakdown": int(out[4]), "estimate_min": float(out[5]), "estimate_max": float(out[6]),
+                "device_ms": float(out[7]), "krylov_dimension": int(out[8]), "setup_ms": float(out[9]),
+                "kappa": hi / lo if lo > 0.0 else float("inf")}
 
     def spmv_bench(self, which: int, reps: int) -> float:
         ms = C.c_double()

@@ -97,6 +97,91 @@ def condition_number_on_device(form, boundary_conditions: List[fd.DirichletBC], 
     return _kappa_on_device(ctx, which, tol, zero_tol)
 
 
+_PC_NAMES = {"jacobi": _ffi.PC_JACOBI, "pph_block2": _ffi.PC_BLOCK2, "ilu": _ffi.PC_ILU, "mg": _ffi.PC_MG, "pph_pmg": _ffi.PC_PMG}
+_BLOCK_PCS = ("jacobi", "ilu", "mg", "pph_pmg")
+_MONOLITHIC_PCS = ("jacobi", "pph_block2", "ilu")
+
+
+def _space_degree(space) -> int:
+    V = space.sub(0) if isinstance(space, fd.MixedFunctionSpace) else space
+    return int(getattr(V, "degree", 1))
+
+
+def _check_preconditioned_pairing(monolithic: bool, space, pc_type: str) -> None:
+    """NotImplementedError for every (operator, pc_type) pairing pph_preconditioned_extremes refuses - raised before any
+    context exists, so a refusal never touches a GPU."""
+    if space.mesh().distributed:
+        raise NotImplementedError("preconditioned condition numbers work on the whole operator on one device: build the mesh "
+                                  "with comm=fd.COMM_SELF under torch.distributed")
+    if pc_type == "none":
+        raise NotImplementedError("pc_type 'none' is the operator itself: use condition_number_on_device")
+    if pc_type == "fieldsplit":
+        raise NotImplementedError("the multiplicative field split is not a symmetric preconditioner: B A has no Lanczos "
+                                  "recurrence; ask for its blocks (effective_condition_numbers)")
+    if pc_type not in _PC_NAMES:
+        raise NotImplementedError(f"pc_type {pc_type!r} is not supported ({', '.join(_PC_NAMES)})")
+    allowed = _MONOLITHIC_PCS if monolithic else _BLOCK_PCS
+    if pc_type not in allowed:
+        what = "the monolithic system" if monolithic else "a scalar block"
+        raise NotImplementedError(f"pc_type {pc_type!r} does not precondition {what} (there: {', '.join(allowed)})")
+    if pc_type == "mg" and _space_degree(space) != 1:
+        raise NotImplementedError("degree-2 spaces have no CG-1-only multigrid hierarchy: pc_type 'mg' is not available; "
+                                  "use 'pph_pmg'")
+
+
+def _pc_kappa(ctx, which: int, pc_type: str, mg_smooth: int, tol: float) -> float:
+    r = ctx.preconditioned_extremes(which, _PC_NAMES[pc_type], mg_smooth=mg_smooth, tol=tol)
+    if not r["converged"]:
+        raise RuntimeError(f"preconditioned Lanczos ({pc_type}) did not converge in {r['iterations']} steps: lambda_min "
+                           f"{r['lambda_min']:.6e} (estimate {r['estimate_min']:.1e}), lambda_max {r['lambda_max']:.6e} "
+                           f"(estimate {r['estimate_max']:.1e})")
+    return float(r["kappa"])
+
+
+def preconditioned_condition_number(form, boundary_conditions: List[fd.DirichletBC], pc_type: str, mg_smooth: int = 2,
+                                    tol: float = 1e-4) -> float:
+    """kappa(B A) = lambda_max / lambda_min of the assembled `form` (the forms get_matrix_data_from_form accepts) under the
+    preconditioner `pc_type` - "jacobi", "pph_block2", "ilu", "mg" or "pph_pmg", the strings translate_options knows - on
+    the FREE rows: what a Krylov method under that preconditioner sees.  Lanczos in the B inner product on the device
+    (pph_preconditioned_extremes): assembled like get_matrix_data_from_form, nothing exported.  A scalar block takes jacobi,
+    ilu, mg (degree 1) and pph_pmg; the monolithic form jacobi, pph_block2 and ilu.  NotImplementedError, before any context
+    exists, for every other pairing, for "fieldsplit" (not symmetric), "none" (condition_number_on_device) and distributed
+    meshes; RuntimeError when the iteration did not converge.  The default tol 1e-4 is four digits of kappa: under multigrid
+    the Ritz residual of the clustered upper end shrinks far more slowly than its value moves."""
+    if not isinstance(form, DPPBilinearForm) and not (isinstance(form, ScalarBlockForm) and form.rank == 2):
+        raise TypeError(f"cannot assemble {type(form)}")
+    _check_preconditioned_pairing(isinstance(form, DPPBilinearForm), form.space, pc_type)
+    ctx, which = _assemble_for(form, boundary_conditions)
+    return _pc_kappa(ctx, which, pc_type, mg_smooth, tol)
+
+
+def effective_condition_numbers(W, params, bcs: List[fd.DirichletBC], solver_parameters: dict, nonlinear: bool = False,
+                                tol: float = 1e-4) -> dict:
+    """The condition numbers the Krylov methods of one option set work against: `solver_parameters` goes through
+    solver.translate_options, and what that configuration preconditions is measured with preconditioned_condition_number's
+    rules.  A monolithic pc_type (jacobi, pph_block2, ilu) gives {"monolithic": kappa(B A)}; a field split or Picard sweeps
+    give {"macro": kappa(B1 A11), "micro": kappa(B2 A22)} for the block preconditioner of the sub-options (pph_mg_smooth
+    honoured).  An LU block (the direct-equivalent solve included) means the block solve is exact: its value is 1.0, returned
+    without touching the device.  pc_type none and a block pc_type none raise NotImplementedError."""
+    from .forms import dpp_form
+    from .solver import translate_options
+
+    cfg, _info = translate_options(solver_parameters, nonlinear=nonlinear)
+    names = {v: k for k, v in _PC_NAMES.items()}
+    split = bool(cfg.picard) or cfg.pc_type == _ffi.PC_FIELDSPLIT
+    if split and cfg.inner_exact:
+        return {"macro": 1.0, "micro": 1.0}
+    pc = cfg.inner_pc_type if split else cfg.pc_type
+    pc_name = names.get(pc, "none")
+    _check_preconditioned_pairing(not split, W, pc_name)
+    a, _L = dpp_form(W, params)
+    ctx, _which = _assemble_for(a, bcs)
+    ns = int(cfg.mg_smooth) if cfg.mg_smooth > 0 else 2
+    if not split:
+        return {"monolithic": _pc_kappa(ctx, _ffi.MAT_MONO, pc_name, ns, tol)}
+    return {"macro": _pc_kappa(ctx, _ffi.MAT_A11, pc_name, ns, tol), "micro": _pc_kappa(ctx, _ffi.MAT_A22, pc_name, ns, tol)}
+
+
 class _FieldView(fd.FunctionSpace):
     def __init__(self, V, field):
         super().__init__(V.mesh(), "CG", getattr(V, "degree", 1))

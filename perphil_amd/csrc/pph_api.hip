@@ -572,6 +572,27 @@ int pph_extreme_eigenvalues(pph_ctx* ctx, int which, double tol, int max_it, int
   return pph_eig_lanczos(ctx, A, tol, max_it, check_every, vec_lo, vec_hi, out);
 }
 
+int pph_preconditioned_extremes(pph_ctx* ctx, int which, int pc_type, int mg_smooth, double tol, int max_it, int check_every,
+                                double* out) {
+  if (!ctx) return PPH_ERR_INVALID;
+  PPH_REQUIRE(ctx, out != nullptr, "out is NULL");
+  PPH_REQUIRE(ctx, ctx->world == 1, "pph_preconditioned_extremes works on a single context (the whole operator on one device)");
+  PPH_REQUIRE(ctx, which == 0 || (which >= 2 && which <= 4),
+              "pph_preconditioned_extremes: which must be 0 (monolithic), 2 (M), 3 (A11) or 4 (A22), the symmetric positive "
+              "definite operators; got %d", which);
+  PPH_HIP(ctx, hipSetDevice(ctx->device));
+  Csr A;   // the operator format pph_spmv would run this product on
+  if (!select_sell_only(ctx, which, &A)) {
+    PPH_TRY(select_csr(ctx, which, &A));
+    PPH_TRY(attach_sell(ctx, which, &A));
+  }
+  PcOperator P;
+  PPH_TRY(pc_operator_prepare(ctx, which, pc_type, mg_smooth, which == 2 ? &A : nullptr, &P));
+  PPH_TRY(pph_eig_pclanczos(ctx, A, P, tol, max_it, check_every, out));
+  if (ctx->mg_lam_pending) PPH_TRY(mg_lam_host(ctx));   // (as at the end of a solve: a bad spectral bound of the hierarchy is an error)
+  return PPH_OK;
+}
+
 __global__ void k_fill_pattern(double* __restrict__ x, int64_t n) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     // cheap deterministic pseudo-random values in (-1, 1)

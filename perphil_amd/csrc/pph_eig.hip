@@ -477,3 +477,191 @@ int pph_eig_lanczos(pph_ctx* ctx, const Csr& A, double tol, int max_it, int chec
   PPH_HIP(ctx, hipGetLastError());
   return PPH_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// K-PCEIG: the extreme eigenvalues of B A (A symmetric positive definite, B a symmetric positive definite preconditioner
+// application) by Lanczos for the pencil (A, B^-1): two sequences u_j and v_j = B u_j with u_i . v_j = delta_ij, so that
+// T = V^T A V is tridiagonal and carries the spectrum of B A.  B^-1 is never applied.
+//
+// One step j, besides the product and the preconditioner: k_lanczos_dot (v.w), k_pclanczos_update (alpha_j from the partial
+// sums, r = w - alpha_j u - beta_{j-1} u_prev over u_prev), k_lanczos_dot (r.z), k_pclanczos_scale (beta_j = sqrt(r.z),
+// u_next = r / beta_j and v_next = z / beta_j in one pass): 16 n + 32 n + 16 n + 32 n = 96 n bytes.  alpha, beta and the raw
+// r.z (whose sign tells an indefinite B from a breakdown) travel through device memory, as in the plain iteration.
+// The iteration runs on the free rows: the start vector is 0 on the constrained ones, the products keep them 0 (unit rows)
+// and pc_operator_apply returns 0 there - the operator the Krylov loops see, whose residuals are 0 on those rows.
+// ------------------------------------------------------------------------------------------------
+// start vector: the hash of k_eig_start, 0 where a mask is set (rows [0, n0) under m0, rows [n0, n) under m1; null: free)
+__global__ __launch_bounds__(256) void k_pceig_start(double* __restrict__ u, int64_t n, const uint8_t* __restrict__ m0,
+                                                     const uint8_t* __restrict__ m1, int64_t n0) {
+  auto value = [&](int64_t i) {
+    const uint8_t* m = i < n0 ? m0 : m1;
+    return (m && m[i < n0 ? i : i - n0]) ? 0.0 : eig_hash(i);
+  };
+  EIG_PAIR_LOOP(p, n) sell_st2(u + 2 * p, value(2 * p), value(2 * p + 1));
+  if (EIG_HAS_TAIL(n)) u[n - 1] = value(n - 1);
+}
+
+// alpha = sum of k_lanczos_dot's partial sums of v.w (every block, k_reduce_final's order); r = w - alpha u - beta u_prev
+// written over u_prev; block 0 stores alpha.  beta_prev null: first step, u_prev is not read.
+__global__ __launch_bounds__(256) void k_pclanczos_update(const double* __restrict__ w, const double* __restrict__ u,
+                                                          double* __restrict__ uprev, int64_t n,
+                                                          const double* __restrict__ part_in, int n_in,
+                                                          const double* __restrict__ beta_prev, double* __restrict__ alpha_out) {
+  __shared__ double lds[4];
+  const double alpha = eig_total_of_partials(part_in, n_in, lds);
+  const bool first = beta_prev == nullptr;
+  const double beta = first ? 0.0 : *beta_prev;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *alpha_out = alpha;
+  EIG_PAIR_LOOP(p, n) {
+    const int64_t i = 2 * p;
+    double w0, w1, u0, u1, q0 = 0.0, q1 = 0.0;
+    sell_ld2(w + i, w0, w1);
+    sell_ld2(u + i, u0, u1);
+    if (!first) sell_ld2(uprev + i, q0, q1);
+    const double r0 = first ? w0 - alpha * u0 : w0 - alpha * u0 - beta * q0;
+    const double r1 = first ? w1 - alpha * u1 : w1 - alpha * u1 - beta * q1;
+    sell_st2(uprev + i, r0, r1);
+  }
+  if (EIG_HAS_TAIL(n)) {
+    const int64_t i = n - 1;
+    uprev[i] = first ? w[i] - alpha * u[i] : w[i] - alpha * u[i] - beta * uprev[i];
+  }
+}
+
+// rz = sum of the partial sums of r.z (every block); beta = sqrt(rz); r *= 1 / beta and z *= 1 / beta in one pass; block 0
+// stores beta and the raw rz (either may be null).  A negative rz gives NaNs that nobody reads: the host refuses the run.
+__global__ __launch_bounds__(256) void k_pclanczos_scale(double* __restrict__ r, double* __restrict__ z, int64_t n,
+                                                         const double* __restrict__ part, int n_part,
+                                                         double* __restrict__ beta_out, double* __restrict__ rz_out) {
+  __shared__ double lds[4];
+  const double rz = eig_total_of_partials(part, n_part, lds);
+  const double beta = sqrt(rz);
+  const double inv = 1.0 / beta;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (beta_out) *beta_out = beta;
+    if (rz_out) *rz_out = rz;
+  }
+  EIG_PAIR_LOOP(p, n) {
+    double a, b;
+    sell_ld2(r + 2 * p, a, b);
+    sell_st2(r + 2 * p, a * inv, b * inv);
+    sell_ld2(z + 2 * p, a, b);
+    sell_st2(z + 2 * p, a * inv, b * inv);
+  }
+  if (EIG_HAS_TAIL(n)) { r[n - 1] *= inv; z[n - 1] *= inv; }
+}
+
+namespace {
+struct PcEigWork {   // everything the call owns: released on every way out
+  DevBuf<double> v[5], ab;
+  double* h = nullptr;   // pinned: alpha[max_it] | beta[max_it] | rz[max_it] | u.v of the start
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~PcEigWork() {
+    for (auto& b : v) b.release();
+    ab.release();
+    if (h) (void)hipHostFree(h);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+};
+}   // namespace
+
+int pph_eig_pclanczos(pph_ctx* ctx, const Csr& A, const PcOperator& P, double tol, int max_it, int check_every, double* out) {
+  if (!(tol > 0.0)) tol = 1e-4;
+  if (max_it <= 0) max_it = 2000;
+  if (check_every <= 0) check_every = 16;
+  const int64_t n = A.nrows;
+  PPH_REQUIRE(ctx, n >= 1 && n == P.nrows, "preconditioned extremes: operator and preconditioner differ in size");
+  const int grid = eig_grid(n);
+  double* const part_a = ctx->scal.p + PPH_MAX_SCAL + (size_t)EIG_PART_AREA * PPH_PART_STRIDE;   // v.w
+  double* const part_z = part_a + PPH_PART_STRIDE;                                                  // r.z
+
+  PcEigWork W;
+  for (auto& b : W.v) PPH_TRY(b.alloc(ctx, (size_t)n));
+  const size_t nab = 3 * (size_t)max_it + 1;
+  PPH_TRY(W.ab.alloc(ctx, nab));
+  PPH_HIP(ctx, hipHostMalloc((void**)&W.h, sizeof(double) * nab, hipHostMallocDefault));
+  PPH_HIP(ctx, hipEventCreate(&W.e0));
+  PPH_HIP(ctx, hipEventCreate(&W.e1));
+  double* const alpha_d = W.ab.p;
+  double* const beta_d = W.ab.p + max_it;
+  double* const rz_d = W.ab.p + 2 * (size_t)max_it;
+  double* const uv_d = W.ab.p + 3 * (size_t)max_it;
+  double* const alpha_h = W.h;
+  double* const beta_h = W.h + max_it;
+  double* const rz_h = W.h + 2 * (size_t)max_it;
+  double* const uv_h = W.h + 3 * (size_t)max_it;
+
+  la_flush_final(ctx);
+  PPH_HIP(ctx, hipEventRecord(W.e0, ctx->stream));
+
+  double *u = W.v[0].p, *uprev = W.v[1].p, *v = W.v[2].p, *w = W.v[3].p, *z = W.v[4].p;
+  // start: u = masked hash, v = B u, both divided by sqrt(u.v)
+  const int64_t n0 = P.mask[1] ? n / 2 : n;
+  hipLaunchKernelGGL(k_pceig_start, dim3(grid), dim3(256), 0, ctx->stream, u, n, P.mask[0], P.mask[1], n0);
+  PPH_TRY(pc_operator_apply(ctx, P, u, v));
+  hipLaunchKernelGGL(k_lanczos_dot, dim3(grid), dim3(256), 0, ctx->stream, (const double*)u, (const double*)v, n, part_z);
+  hipLaunchKernelGGL(k_pclanczos_scale, dim3(grid), dim3(256), 0, ctx->stream, u, v, n, (const double*)part_z, grid,
+                     (double*)nullptr, uv_d);
+  PPH_HIP(ctx, hipMemcpyAsync(uv_h, uv_d, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  PPH_REQUIRE(ctx, *uv_h != 0.0, "preconditioned extremes: no free rows (every row of the operator is constrained)");
+  // (u.v carries the units of B, not those of B A: the sign rule of the steps has no scale for it, any negative value is one)
+  PPH_REQUIRE(ctx, *uv_h > 0.0 && isfinite(*uv_h),
+              "preconditioned extremes: the preconditioner is not positive definite on the Krylov space (start: u.Bu = %.3e)", *uv_h);
+
+  double th[2] = {0, 0}, est[2] = {0, 0};
+  bool conv[2] = {false, false};
+  bool breakdown = false;
+  int m = 0, mt = 0;
+  std::vector<double> xs[2];   // eigenvectors of T of the two ends
+  while (true) {
+    const int m1 = (m + check_every < max_it) ? m + check_every : max_it;
+    for (int j = m; j < m1; ++j) {
+      la_spmv(ctx, A, v, w);
+      hipLaunchKernelGGL(k_lanczos_dot, dim3(grid), dim3(256), 0, ctx->stream, (const double*)v, (const double*)w, n, part_a);
+      hipLaunchKernelGGL(k_pclanczos_update, dim3(grid), dim3(256), 0, ctx->stream, (const double*)w, (const double*)u, uprev, n,
+                         (const double*)part_a, grid, j > 0 ? beta_d + (j - 1) : (const double*)nullptr, alpha_d + j);
+      PPH_TRY(pc_operator_apply(ctx, P, uprev, z));
+      hipLaunchKernelGGL(k_lanczos_dot, dim3(grid), dim3(256), 0, ctx->stream, (const double*)uprev, (const double*)z, n, part_z);
+      hipLaunchKernelGGL(k_pclanczos_scale, dim3(grid), dim3(256), 0, ctx->stream, uprev, z, n, (const double*)part_z, grid,
+                         beta_d + j, rz_d + j);
+      double* t = u; u = uprev; uprev = t;   // the scaled r is the new u, the old u the new u_prev
+      t = v; v = z; z = t;                   // the scaled z is the new v; the old v's buffer receives the next z
+    }
+    m = m1;
+    PPH_HIP(ctx, hipMemcpyAsync(W.h, W.ab.p, sizeof(double) * nab, hipMemcpyDeviceToHost, ctx->stream));
+    PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // per step, in order: the sign of r.z (B not positive definite: refused), then the breakdown test of the plain iteration
+    double scale = isfinite(beta_h[0]) ? beta_h[0] : 0.0;
+    mt = m;
+    for (int j = 0; j < m; ++j) {
+      scale = fmax(scale, fabs(alpha_h[j]));
+      PPH_REQUIRE(ctx, !(rz_h[j] < -EIG_BREAKDOWN * scale * scale),
+                  "preconditioned extremes: the preconditioner is not positive definite on the Krylov space (step %d: r.Br = %.3e)",
+                  j, rz_h[j]);
+      if (!isfinite(beta_h[j]) || !(beta_h[j] > EIG_BREAKDOWN * scale)) { mt = j + 1; breakdown = true; break; }
+    }
+    PPH_REQUIRE(ctx, eig_tridiag_extremes(alpha_h, beta_h, mt, &th[0], &th[1], breakdown ? nullptr : &xs[0], breakdown ? nullptr : &xs[1]),
+                "preconditioned Lanczos: the operator or the preconditioner produced values that are not finite (step %d)", mt);
+    if (breakdown) {
+      est[0] = est[1] = 0.0;
+      conv[0] = conv[1] = true;
+      break;
+    }
+    for (int e = 0; e < 2; ++e) {
+      est[e] = fabs(beta_h[m - 1] * xs[e][m - 1]);
+      if (est[e] <= tol * fabs(th[e])) conv[e] = true;   // (latched, as in pph_eig_lanczos)
+    }
+    if ((conv[0] && conv[1]) || m >= max_it) break;
+  }
+  PPH_HIP(ctx, hipEventRecord(W.e1, ctx->stream));
+  PPH_HIP(ctx, hipEventSynchronize(W.e1));
+  float ms = 0.f;
+  PPH_HIP(ctx, hipEventElapsedTime(&ms, W.e0, W.e1));
+  for (int i = 0; i < 10; ++i) out[i] = 0.0;
+  out[0] = th[0]; out[1] = th[1]; out[2] = (double)m; out[3] = (conv[0] && conv[1]) ? 1.0 : 0.0; out[4] = breakdown ? 1.0 : 0.0;
+  out[5] = est[0]; out[6] = est[1]; out[7] = (double)ms; out[8] = (double)mt; out[9] = P.setup_ms;
+  PPH_HIP(ctx, hipGetLastError());
+  return PPH_OK;
+}

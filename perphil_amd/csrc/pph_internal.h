@@ -761,6 +761,27 @@ static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b;
 // extreme eigenvalues of a symmetric operator by plain Lanczos (pph_eig.hip; out as pph_extreme_eigenvalues documents it)
 int pph_eig_lanczos(pph_ctx* ctx, const Csr& A, double tol, int max_it, int check_every, double* vec_lo, double* vec_hi,
                     double* out);
+// one block preconditioner applied to a device vector (pph_solve.hip: what pph_pc_apply / pph_pc_bench run).  which: 0 the A11
+// block, 1 the A22 block; pc_apply_prepare checks the pairing, resolves PPH_PC_PMG at degree 1 and builds the hierarchy / the
+// CSR values; pc_apply_device: z = B r (dinv_work: n doubles, used by PPH_PC_JACOBI)
+int pc_apply_prepare(pph_ctx* ctx, int which, int* pc_type);
+int pc_apply_device(pph_ctx* ctx, int which, int pc_type, int ns, const double* r, double* z, double* dinv_work);
+// a symmetric preconditioner B of one operator of the context, set up once and applied many times (pph_solve.hip; the
+// preconditioned Lanczos iteration of pph_eig.hip).  which: pph_get_csr's selector (0 monolithic, 2 M, 3 A11, 4 A22)
+struct PcOperator {
+  int which = 0, pc_type = 0, ns = 2;
+  int64_t nrows = 0;
+  DevBuf<double> data;                           // Jacobi: 1 / diag [nrows]; PPH_PC_BLOCK2: the inverted 2 x 2 blocks [4][n]
+  const uint8_t* mask[2] = {nullptr, nullptr};   // constrained rows of the one or two field segments (null: none)
+  double setup_ms = 0.0;                         // host ms of the hierarchy / factorisation this set-up had to build (else 0)
+  ~PcOperator() { data.release(); }
+};
+// M: the mass matrix with CSR values (which == 2 only).  Refuses every pairing pph_preconditioned_extremes documents as invalid
+int pc_operator_prepare(pph_ctx* ctx, int which, int pc_type, int mg_smooth, const Csr* M, PcOperator* P);
+// z = B r, set to 0 on the constrained rows; r must be 0 there
+int pc_operator_apply(pph_ctx* ctx, const PcOperator& P, const double* r, double* z);
+// extreme eigenvalues of B A by Lanczos in the B inner product (pph_eig.hip; out as pph_preconditioned_extremes documents it)
+int pph_eig_pclanczos(pph_ctx* ctx, const Csr& A, const PcOperator& P, double tol, int max_it, int check_every, double* out);
 // p-multigrid (pph_pmg.hip): the passes over the degree-2 level of a PPH_PC_PMG cycle
 bool pmg_level0_ok(const pph_ctx* ctx, const Csr& A);   // the tile kernels serve this operator (else: the generic composition)
 // t = A d; r -= t; dnew = c1 d + c2 dinv r; x += dnew   (one Chebyshev-Jacobi step; dnew != d)

@@ -1076,7 +1076,7 @@ int pph_solve(pph_ctx* ctx, const pph_solver_cfg* cfg, double* x_host, pph_solve
 }
 
 // ---- one block preconditioner, applied to a caller's vector (parity checks of the cycle itself) ----------------------
-static int pc_apply_prepare(pph_ctx* ctx, int which, int* pc_type) {
+int pc_apply_prepare(pph_ctx* ctx, int which, int* pc_type) {
   PPH_REQUIRE(ctx, ctx->asm_ok, "pph_pc_apply before pph_assemble_dpp");
   PPH_REQUIRE(ctx, which == 0 || which == 1, "pph_pc_apply: which must be 0 (A11) or 1 (A22)");
   PPH_REQUIRE(ctx, ctx->world == 1, "pph_pc_apply: single context only");
@@ -1091,7 +1091,7 @@ static int pc_apply_prepare(pph_ctx* ctx, int which, int* pc_type) {
   return PPH_OK;
 }
 
-static int pc_apply_device(pph_ctx* ctx, int which, int pc_type, int ns, const double* r, double* z, double* dinv_work) {
+int pc_apply_device(pph_ctx* ctx, int which, int pc_type, int ns, const double* r, double* z, double* dinv_work) {
   if (pc_type == PPH_PC_JACOBI) {
     la_extract_diag_inv(ctx, block_csr(ctx, which), dinv_work);
     la_pointwise_mult(ctx, z, dinv_work, r, ctx->n);
@@ -1101,6 +1101,91 @@ static int pc_apply_device(pph_ctx* ctx, int which, int pc_type, int ns, const d
     PPH_REQUIRE(ctx, ilu_apply(ctx, ctx->ilu[1 + which], r, z) >= 0, "pph_pc_apply: ILU(0) application failed");
   } else {
     mg_vcycle(ctx, which, r, z, ns);
+  }
+  return PPH_OK;
+}
+
+// ---- a preconditioner set up once and applied per step (pph_eig_pclanczos) -------------------------------------------------
+// The block cases go through pc_apply_prepare / pc_apply_device; what pc_apply_device redoes per application (the Jacobi
+// diagonal) is taken once here.  The monolithic cases are those of pph_solve_device (Jacobi, 2 x 2 block-Jacobi, ILU(0) on
+// ctx->ilu[0]), with data of their own so that a later solve finds its work vectors untouched.
+int pc_operator_prepare(pph_ctx* ctx, int which, int pc_type, int mg_smooth, const Csr* M, PcOperator* P) {
+  const char* fn = "pph_preconditioned_extremes";
+  PPH_REQUIRE(ctx, ctx->world == 1, "%s works on a single context (the whole operator on one device)", fn);
+  PPH_REQUIRE(ctx, which == 0 || (which >= 2 && which <= 4),
+              "%s: which must be 0 (monolithic), 2 (M), 3 (A11) or 4 (A22), the symmetric positive definite operators; got %d", fn, which);
+  PPH_REQUIRE(ctx, pc_type != PPH_PC_NONE, "%s: pc_type none is the operator itself: use pph_extreme_eigenvalues", fn);
+  PPH_REQUIRE(ctx, pc_type != PPH_PC_FIELDSPLIT,
+              "%s: the multiplicative field split is not a symmetric preconditioner: B A has no Lanczos recurrence", fn);
+  PPH_REQUIRE(ctx, which == 2 || ctx->asm_ok, "%s before pph_assemble_dpp", fn);
+  const int64_t n = ctx->n;
+  P->which = which; P->ns = mg_smooth > 0 ? mg_smooth : 2;
+  P->nrows = which == 0 ? 2 * n : n;
+  P->setup_ms = 0.0;
+  PPH_HIP(ctx, hipSetDevice(ctx->device));
+  PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const auto t0 = std::chrono::steady_clock::now();
+  bool built = false;
+  if (which == 3 || which == 4) {
+    const int f = which - 3;
+    PPH_REQUIRE(ctx, pc_type == PPH_PC_JACOBI || pc_type == PPH_PC_ILU || pc_type == PPH_PC_MG || pc_type == PPH_PC_PMG,
+                "%s: pc_type %d is no symmetric preconditioner of a scalar block (jacobi, ilu, mg, pph_pmg)", fn, pc_type);
+    built = ((pc_type == PPH_PC_MG || pc_type == PPH_PC_PMG) && !ctx->mg_ok) || (pc_type == PPH_PC_ILU && !ctx->ilu[1 + f].valid);
+    PPH_TRY(pc_apply_prepare(ctx, f, &pc_type));
+    if (pc_type == PPH_PC_JACOBI) {
+      PPH_TRY(P->data.alloc(ctx, (size_t)n));
+      la_extract_diag_inv(ctx, block_csr(ctx, f), P->data.p);
+    } else if (pc_type == PPH_PC_ILU) {
+      if (!ctx->ilu[1 + f].valid) PPH_TRY(ilu_factor(ctx, ctx->ilu[1 + f], block_csr(ctx, f)));
+    }
+    P->mask[0] = ctx->bcmask[f].p;
+  } else if (which == 0) {
+    PPH_REQUIRE(ctx, ctx->mono_ok, "monolithic CSR not assembled (pph_assemble_dpp(..., monolithic=1))");
+    PPH_REQUIRE(ctx, pc_type == PPH_PC_JACOBI || pc_type == PPH_PC_BLOCK2 || pc_type == PPH_PC_ILU,
+                "%s: pc_type %d is no symmetric preconditioner of the monolithic system (jacobi, pph_block2, ilu)", fn, pc_type);
+    const Csr A = mono_csr(ctx);
+    if (pc_type == PPH_PC_JACOBI) {
+      PPH_TRY(P->data.alloc(ctx, (size_t)(2 * n)));
+      la_extract_diag_inv(ctx, A, P->data.p);
+    } else if (pc_type == PPH_PC_BLOCK2) {
+      PPH_TRY(pph_ensure_csr_blocks(ctx));
+      PPH_TRY(P->data.alloc(ctx, (size_t)(4 * n)));
+      const int grid = (int)(ceil_div64(n, 256) < 2048 ? ceil_div64(n, 256) : 2048);
+      hipLaunchKernelGGL(k_block2_build, dim3(grid), dim3(256), 0, ctx->stream, ctx->mesh.rowptr.p, ctx->mesh.col.p,
+                         ctx->A11.p, ctx->A22.p, ctx->A12.p, ctx->A21p(), n, P->data.p);
+    } else {
+      built = !ctx->ilu[0].valid;
+      if (built) PPH_TRY(ilu_factor(ctx, ctx->ilu[0], A));
+    }
+    P->mask[0] = ctx->bcmask[0].p;
+    P->mask[1] = ctx->bcmask[1].p;
+  } else {
+    PPH_REQUIRE(ctx, pc_type == PPH_PC_JACOBI, "%s: the mass matrix takes pc_type jacobi only; got %d", fn, pc_type);
+    PPH_REQUIRE(ctx, M && M->val && M->nrows == n, "%s: the mass matrix needs its CSR values", fn);
+    PPH_TRY(P->data.alloc(ctx, (size_t)n));
+    la_extract_diag_inv(ctx, *M, P->data.p);
+  }
+  P->pc_type = pc_type;
+  PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  PPH_HIP(ctx, hipGetLastError());
+  if (built) P->setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PPH_OK;
+}
+
+int pc_operator_apply(pph_ctx* ctx, const PcOperator& P, const double* r, double* z) {
+  const int64_t n = ctx->n;
+  if (P.pc_type == PPH_PC_JACOBI) {
+    la_pointwise_mult(ctx, z, P.data.p, r, P.nrows);
+    return PPH_OK;   // (r is 0 on the constrained rows, so is z)
+  }
+  if (P.which == 0) {
+    if (P.pc_type == PPH_PC_BLOCK2) la_block2_apply(ctx, z, P.data.p, r, n);
+    else PPH_REQUIRE(ctx, ilu_apply(ctx, ctx->ilu[0], r, z) >= 0, "pph_preconditioned_extremes: ILU(0) application failed");
+    pmg_zero_masked(ctx, z, P.mask[0], n);
+    pmg_zero_masked(ctx, z + n, P.mask[1], n);
+  } else {
+    PPH_TRY(pc_apply_device(ctx, P.which - 3, P.pc_type, P.ns, r, z, nullptr));
+    pmg_zero_masked(ctx, z, P.mask[0], n);
   }
   return PPH_OK;
 }
