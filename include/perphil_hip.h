@@ -62,12 +62,23 @@ enum {
   PPH_PC_MG = 4,          /* geometric multigrid V-cycle (scalar blocks; inside fieldsplit/Picard) */
   PPH_PC_ILU = 5,         /* pc_type ilu, pc_factor_levels 0: ILU(0) in the natural row order, level-scheduled
                            * (monolithic system, or the scalar blocks inside fieldsplit / Picard); single context */
-  PPH_PC_PMG = 6          /* pph_pmg (scalar blocks; inside fieldsplit / Picard, as inner_pc_type): one symmetric V-cycle whose
+  PPH_PC_PMG = 6,         /* pph_pmg (scalar blocks; inside fieldsplit / Picard, as inner_pc_type): one symmetric V-cycle whose
                            * top level is the context's own operator and whose lower levels are the CG-1 geometric hierarchy
                            * on the same cells.  Degree 2: mg_smooth Chebyshev-Jacobi steps on the Q2 / P2 operator, restriction
                            * to the CG-1 space of the same cells (the degree-2 nodes are the CG-1 nodes of the mesh refined
                            * once, so this is the h-transfer stencil), the PPH_PC_MG cycle there, and back.  Degree 1: there is
                            * no p-level to add, PPH_PC_PMG is PPH_PC_MG. */
+  PPH_PC_CMG = 7          /* pph_cmg (monolithic system; pc_type of a cg / gmres / preonly solve with picard == 0): one symmetric
+                           * V-cycle on the coupled 2n x 2n system over the CG-1 hierarchy of PPH_PC_MG.  Level operator
+                           * A_l = [[A11_l, C_l], [C_l^T, A22_l]] with the level operators of the scalar cycle on the diagonal
+                           * and C_l = -(beta/mu) F0 M_l F1 (M_l the level's mass matrix, F_f zeroes the constrained dofs of
+                           * field f); smoother: mg_smooth Chebyshev steps on [lam_l / 4, lam_l] under the inverse of the 2 x 2
+                           * block of the two pressures of every node (diagonal where either field is constrained), lam_l the
+                           * largest absolute row sum of D_l^-1 A_l; transfers: those of PPH_PC_MG per field, each with its own
+                           * masks; coarsest level: CG on A_L under D_L^-1 to rtol 1e-12, limited by option coarse_max_it (a
+                           * solve that stops short is reported as inner_failed); a mesh that cannot be coarsened: max(mg_smooth,
+                           * 2) Chebyshev steps.  fp64, no floating-point atomics.  Refused (PPH_ERR_INVALID with a message) as
+                           * inner_pc_type, with picard, on a degree-2 context and with world != 1. */
 };
 
 typedef struct {
@@ -89,8 +100,8 @@ typedef struct {
   double picard_rtol;    /* snes_rtol */
   double picard_atol;    /* snes_atol */
   int32_t picard_max_it; /* snes_max_it */
-  int32_t mg_smooth;     /* smoothing steps per level side for PPH_PC_MG / PPH_PC_PMG (default 2; every level, the
-                          * degree-2 one included) */
+  int32_t mg_smooth;     /* smoothing steps per level side for PPH_PC_MG / PPH_PC_PMG / PPH_PC_CMG (default 2; every level,
+                          * the degree-2 one included) */
   double inner_reduction; /* > 0: block solves stop once their preconditioned residual has dropped by this
                           * factor from its value at the start of the solve (inexact Picard sweeps; warm
                           * starts make the sequence converge to the exact fixed point), or at inner_rtol,
@@ -214,6 +225,15 @@ int pph_spmv_bench(pph_ctx* ctx, int which, int reps, double* avg_ms);
  * there.  PPH_PC_MG on a degree-2 context returns PPH_ERR_INVALID, PPH_PC_PMG on a degree-1 context is PPH_PC_MG.  Single
  * context only. */
 int pph_pc_apply(pph_ctx* ctx, int which, int pc_type, int mg_smooth, const double* r_host, double* z_host);
+/* z = B r: ONE application of a preconditioner of the monolithic system to a host vector of 2n entries (field-major), for
+ * parity checks of the coupled cycle itself.  pc_type: PPH_PC_CMG | PPH_PC_BLOCK2 | PPH_PC_JACOBI; mg_smooth as in
+ * pph_solver_cfg (<= 0: 2).  Needs the monolithic assembly.  The entries of r on constrained dofs are taken as 0; the
+ * result is 0 there.  Single context, degree 1 for PPH_PC_CMG. */
+int pph_pc_apply_coupled(pph_ctx* ctx, int pc_type, int mg_smooth, const double* r_host /* 2n */, double* z_host /* 2n */);
+/* diagnostic (tools/cmg_probe.py): `reps` PPH_PC_CMG cycles on a device-resident vector of ones and `reps` fine-level
+ * passes of the coupled smoothing kernel alone, timed with HIP events.  out4: ms per cycle; ms per such pass; its
+ * algorithmic bytes; ms of set-up the call had to do first */
+int pph_cmg_bench(pph_ctx* ctx, int mg_smooth, int reps, double* out4);
 /* diagnostic (tools/pmg_probe.py): `reps` applications to a device-resident vector of ones, timed with HIP events.
  * out4: ms per application; ms of it in the passes over the degree-2 level (PPH_PC_PMG at degree 2, else 0); bytes those
  * passes move per application (the kernels of pph_pmg.hip, else 0); ms of set-up the call had to do first */
@@ -263,7 +283,7 @@ int pph_extreme_eigenvalues(pph_ctx* ctx, int which, double tol, int max_it, int
  * reorthogonalisation.
  * which / pc_type (everything else, or world != 1: PPH_ERR_INVALID with a message):
  *   3 (A11), 4 (A22): PPH_PC_JACOBI, PPH_PC_ILU, PPH_PC_MG (degree-1 contexts only), PPH_PC_PMG (at degree 1 it is PPH_PC_MG);
- *   0 (monolithic, needs monolithic assembly): PPH_PC_JACOBI, PPH_PC_BLOCK2, PPH_PC_ILU;
+ *   0 (monolithic, needs monolithic assembly): PPH_PC_JACOBI, PPH_PC_BLOCK2, PPH_PC_ILU, PPH_PC_CMG (degree-1 contexts);
  *   2 (M): PPH_PC_JACOBI.
  * PPH_PC_NONE is refused (that is pph_extreme_eigenvalues), PPH_PC_FIELDSPLIT as well (the multiplicative split is not
  * symmetric).  mg_smooth as in pph_solver_cfg (<= 0: 2).

@@ -23,7 +23,7 @@ LIB_PATH = os.environ.get("PERPHIL_HIP_LIB") or os.path.join(_HERE, "libperphil_
 PPH_OK, PPH_ERR_INVALID, PPH_ERR_HIP, PPH_ERR_NOMEM, PPH_ERR_DIVERGED, PPH_ERR_COMM = 0, -1, -2, -3, -4, -5
 CELL_QUAD, CELL_TRI, CELL_HEX, CELL_TET = 0, 1, 2, 3
 KSP_PREONLY, KSP_CG, KSP_GMRES = 0, 1, 2
-PC_NONE, PC_JACOBI, PC_BLOCK2, PC_FIELDSPLIT, PC_MG, PC_ILU, PC_PMG = 0, 1, 2, 3, 4, 5, 6
+PC_NONE, PC_JACOBI, PC_BLOCK2, PC_FIELDSPLIT, PC_MG, PC_ILU, PC_PMG, PC_CMG = 0, 1, 2, 3, 4, 5, 6, 7
 MAT_MONO, MAT_K, MAT_M, MAT_A11, MAT_A22, MAT_A12, MAT_A21 = 0, 1, 2, 3, 4, 5, 6
 
 # every symbol include/perphil_hip.h declares (checked by tests/test_abi.py)
@@ -39,7 +39,7 @@ EXPORTS = [
     "pph_darcy_velocity",
     "pph_get_stream", "pph_copy_solution_device", "pph_set_dirichlet_device", "pph_error_norms_mms_device",
     "pph_error_norms_sampled_device", "pph_darcy_velocity_device",
-    "pph_pc_apply", "pph_pc_bench", "pph_asm_wave_map",
+    "pph_pc_apply", "pph_pc_bench", "pph_asm_wave_map", "pph_pc_apply_coupled", "pph_cmg_bench",
     "pph_eval_points", "pph_eval_points_device",
     "pph_integrate", "pph_integrate_device", "pph_boundary_flux", "pph_boundary_flux_device",
     "pph_dpp_nodal_flux", "pph_dpp_nodal_flux_device",
@@ -183,6 +183,8 @@ def _load() -> C.CDLL:
         "pph_darcy_velocity_device": ([p, C.c_void_p, C.c_double, C.c_void_p], C.c_int),
         "pph_pc_apply": ([p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
         "pph_pc_bench": ([p, C.c_int, C.c_int, C.c_int, C.c_int, f64p], C.c_int),
+        "pph_pc_apply_coupled": ([p, C.c_int, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
+        "pph_cmg_bench": ([p, C.c_int, C.c_int, f64p], C.c_int),
         "pph_asm_wave_map": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, i64p], C.c_int),
         "pph_eval_points": ([p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, i64p], C.c_int),
         "pph_eval_points_device": ([p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, i64p],
@@ -667,6 +669,22 @@ class Context:
         self._check(lib.pph_pc_apply(self._h, int(which), int(pc_type), int(mg_smooth), _ptr(r), _ptr(z)))
         return z
 
+    def pc_apply_coupled(self, pc_type: int, r: np.ndarray, mg_smooth: int = 2) -> np.ndarray:
+        """z = B r: one application of the monolithic preconditioner `pc_type` (PC_CMG, PC_BLOCK2, PC_JACOBI) to a
+        field-major vector of 2n entries (needs the monolithic assembly).  Entries of r on constrained dofs count as 0."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        if r.shape != (2 * self.n,):
+            raise ValueError(f"pc_apply_coupled: r must have shape ({2 * self.n},)")
+        z = np.empty_like(r)
+        self._check(lib.pph_pc_apply_coupled(self._h, int(pc_type), int(mg_smooth), _ptr(r), _ptr(z)))
+        return z
+
+    def cmg_bench(self, reps: int, mg_smooth: int = 2) -> dict:
+        """Timing of `reps` coupled cycles and of the fine-level coupled smoothing kernel alone (tools/cmg_probe.py)."""
+        out = np.zeros(4, dtype=np.float64)
+        self._check(lib.pph_cmg_bench(self._h, int(mg_smooth), int(reps), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return {"cycle_ms": out[0], "step_ms": out[1], "step_bytes": out[2], "setup_ms": out[3]}
+
     def pc_bench(self, which: int, pc_type: int, reps: int, mg_smooth: int = 2) -> dict:
         """Timing of `reps` applications of a block preconditioner on the device (tools/pmg_probe.py)."""
         out = np.zeros(4, dtype=np.float64)
@@ -703,7 +721,7 @@ class Context:
                                 check_every: int = 16) -> dict:
         """lambda_min and lambda_max of B A on the free rows - A the operator `which` (MAT_MONO, MAT_M, MAT_A11, MAT_A22), B
         the symmetric preconditioner `pc_type` (blocks: PC_JACOBI, PC_ILU, PC_MG, PC_PMG; monolithic: PC_JACOBI, PC_BLOCK2,
-        PC_ILU; M: PC_JACOBI) - by Lanczos in the B inner product on the device (pph_preconditioned_extremes).  Returns the
+        PC_ILU, PC_CMG; M: PC_JACOBI) - by Lanczos in the B inner product on the device (pph_preconditioned_extremes).  Returns the
         keys of extreme_eigenvalues plus `setup_ms` (the preconditioner's set-up, 0 when it was up to date) and `kappa` =
         lambda_max / lambda_min (inf when lambda_min is not positive); `converged` 0 means stopped at max_it."""
         out = np.zeros(10, dtype=np.float64)

@@ -97,9 +97,10 @@ def condition_number_on_device(form, boundary_conditions: List[fd.DirichletBC], 
     return _kappa_on_device(ctx, which, tol, zero_tol)
 
 
-_PC_NAMES = {"jacobi": _ffi.PC_JACOBI, "pph_block2": _ffi.PC_BLOCK2, "ilu": _ffi.PC_ILU, "mg": _ffi.PC_MG, "pph_pmg": _ffi.PC_PMG}
+_PC_NAMES = {"jacobi": _ffi.PC_JACOBI, "pph_block2": _ffi.PC_BLOCK2, "ilu": _ffi.PC_ILU, "mg": _ffi.PC_MG, "pph_pmg": _ffi.PC_PMG,
+             "pph_cmg": _ffi.PC_CMG}
 _BLOCK_PCS = ("jacobi", "ilu", "mg", "pph_pmg")
-_MONOLITHIC_PCS = ("jacobi", "pph_block2", "ilu")
+_MONOLITHIC_PCS = ("jacobi", "pph_block2", "ilu", "pph_cmg")
 
 
 def _space_degree(space) -> int:
@@ -127,6 +128,8 @@ def _check_preconditioned_pairing(monolithic: bool, space, pc_type: str) -> None
     if pc_type == "mg" and _space_degree(space) != 1:
         raise NotImplementedError("degree-2 spaces have no CG-1-only multigrid hierarchy: pc_type 'mg' is not available; "
                                   "use 'pph_pmg'")
+    if pc_type == "pph_cmg" and _space_degree(space) != 1:
+        raise NotImplementedError("pc_type 'pph_cmg' is a cycle on the CG-1 multigrid hierarchy: degree-2 spaces have none")
 
 
 def _pc_kappa(ctx, which: int, pc_type: str, mg_smooth: int, tol: float) -> float:
@@ -141,10 +144,10 @@ def _pc_kappa(ctx, which: int, pc_type: str, mg_smooth: int, tol: float) -> floa
 def preconditioned_condition_number(form, boundary_conditions: List[fd.DirichletBC], pc_type: str, mg_smooth: int = 2,
                                     tol: float = 1e-4) -> float:
     """kappa(B A) = lambda_max / lambda_min of the assembled `form` (the forms get_matrix_data_from_form accepts) under the
-    preconditioner `pc_type` - "jacobi", "pph_block2", "ilu", "mg" or "pph_pmg", the strings translate_options knows - on
+    preconditioner `pc_type` - "jacobi", "pph_block2", "ilu", "mg", "pph_pmg" or "pph_cmg", the strings translate_options knows - on
     the FREE rows: what a Krylov method under that preconditioner sees.  Lanczos in the B inner product on the device
     (pph_preconditioned_extremes): assembled like get_matrix_data_from_form, nothing exported.  A scalar block takes jacobi,
-    ilu, mg (degree 1) and pph_pmg; the monolithic form jacobi, pph_block2 and ilu.  NotImplementedError, before any context
+    ilu, mg (degree 1) and pph_pmg; the monolithic form jacobi, pph_block2, ilu and pph_cmg (degree 1).  NotImplementedError, before any context
     exists, for every other pairing, for "fieldsplit" (not symmetric), "none" (condition_number_on_device) and distributed
     meshes; RuntimeError when the iteration did not converge.  The default tol 1e-4 is four digits of kappa: under multigrid
     the Ritz residual of the clustered upper end shrinks far more slowly than its value moves."""
@@ -159,7 +162,7 @@ def effective_condition_numbers(W, params, bcs: List[fd.DirichletBC], solver_par
                                 tol: float = 1e-4) -> dict:
     """The condition numbers the Krylov methods of one option set work against: `solver_parameters` goes through
     solver.translate_options, and what that configuration preconditions is measured with preconditioned_condition_number's
-    rules.  A monolithic pc_type (jacobi, pph_block2, ilu) gives {"monolithic": kappa(B A)}; a field split or Picard sweeps
+    rules.  A monolithic pc_type (jacobi, pph_block2, ilu, pph_cmg) gives {"monolithic": kappa(B A)}; a field split or Picard sweeps
     give {"macro": kappa(B1 A11), "micro": kappa(B2 A22)} for the block preconditioner of the sub-options (pph_mg_smooth
     honoured).  An LU block (the direct-equivalent solve included) means the block solve is exact: its value is 1.0, returned
     without touching the device.  pc_type none and a block pc_type none raise NotImplementedError."""

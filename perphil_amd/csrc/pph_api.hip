@@ -589,6 +589,7 @@ int pph_preconditioned_extremes(pph_ctx* ctx, int which, int pc_type, int mg_smo
   PcOperator P;
   PPH_TRY(pc_operator_prepare(ctx, which, pc_type, mg_smooth, which == 2 ? &A : nullptr, &P));
   PPH_TRY(pph_eig_pclanczos(ctx, A, P, tol, max_it, check_every, out));
+  if (pc_type == PPH_PC_CMG) PPH_TRY(cmg_collect_failures(ctx));   // (cleared: coarsest solves that stopped short belong to no solve)
   if (ctx->mg_lam_pending) PPH_TRY(mg_lam_host(ctx));   // (as at the end of a solve: a bad spectral bound of the hierarchy is an error)
   return PPH_OK;
 }

@@ -338,6 +338,17 @@ struct MgLevel {
   double lam[2] = {0, 0};        // upper bound of the spectrum of D^-1 A
 };
 
+// one level of the coupled cycle PPH_PC_CMG (pph_cmg.hip), on top of level l of the hierarchy above
+struct CmgLevel {
+  DevBuf<double> K, M;             // stiffness and mass matrix of the level's mesh on its CSR pattern (mesh only: kept while the hierarchy stands)
+  bool km_ok = false;
+  const double *Kp = nullptr, *Mp = nullptr;   // what the kernels read: these, or the mesh's own K and M while it holds valid ones
+  DevBuf<double> binv;             // [4][n] inverted 2 x 2 blocks of the two pressures of a node (layout of la_block2_apply)
+  DevBuf<double> x, b, r, d, e, t; // [2n] work vectors, field-major (x unused on level 0; d / e: the direction and its successor)
+  DevBuf<double> cval[4];          // coarsest level: A11, A22, C, C^T as CSR values on the scalar pattern (the one-workgroup CG)
+  double lam = 0;                  // largest absolute row sum of D^-1 A
+};
+
 // captured iteration bodies (pph_la.hip: la_run_graph): valid while every pointer baked into the kernels' arguments is
 struct GraphKey {
   const void* p[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -494,6 +505,13 @@ struct pph_ctx {
   uint64_t mg_epoch = 0;                // bumped whenever the hierarchy's buffers are (re)allocated: captured graphs die
   bool mg_ok = false;                   // hierarchy values (operators, masks, bounds) match the assembled system
   bool mg_struct_ok = false;            // hierarchy structure (level meshes, patterns, buffers) matches mesh + communicator
+  uint64_t mg_values_epoch = 0;         // counts the set-ups mg_setup actually ran (new assembly / Dirichlet sets / hierarchy)
+  // coupled multigrid (PPH_PC_CMG, pph_cmg.hip): per-level blocks, bounds and work vectors; valid while cmg_epoch == mg_values_epoch
+  std::vector<CmgLevel> cmg;
+  DevBuf<unsigned long long> cmg_lam;   // the levels' bounds as bit patterns (integer atomic max)
+  DevBuf<unsigned long long> cmg_rec;   // [0] coarsest solves on the device that stopped short (cmg_collect_failures)
+  uint64_t cmg_epoch = 0;
+  bool cmg_ok = false;
 
   // timers (ms)
   double t_mesh = 0, t_asm = 0, t_bc = 0, t_solve = 0;
@@ -757,6 +775,19 @@ void mg_vcycle(pph_ctx* ctx, int which, const double* r, double* z, int nsmooth)
 bool mg_pre_smoother(pph_ctx* ctx, int which, int nsmooth, const double** dinv, const double** w /* device */,
                      bool* launch_only);
 
+// the hierarchy's products and transfers for one field (single context): what the coupled cycle is composed of
+Csr mg_level_csr(const pph_ctx* ctx, int l, int which);
+void mg_restrict_field(pph_ctx* ctx, int l, int which, const double* rf, double* bc);
+void mg_prolong_add_field(pph_ctx* ctx, int l, int which, double* xf, const double* xc);
+// coupled multigrid (pph_cmg.hip): set-up after mg_setup (no-op while up to date); z = B r for vectors of 2n, r taken as 0 on
+// constrained dofs; coarsest solves that stopped short since the last call are added to ctx->coarse_failed
+int cmg_setup(pph_ctx* ctx);
+int cmg_apply(pph_ctx* ctx, const double* r, double* z, int nsmooth);
+int cmg_collect_failures(pph_ctx* ctx);
+void cmg_release(pph_ctx* ctx);
+double cmg_step_bytes(const pph_ctx* ctx);
+int cmg_step_bench(pph_ctx* ctx, int reps, double* ms_out);   // ms per fine-level pass of k_cmg_row (mode 0) alone
+
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // extreme eigenvalues of a symmetric operator by plain Lanczos (pph_eig.hip; out as pph_extreme_eigenvalues documents it)
 int pph_eig_lanczos(pph_ctx* ctx, const Csr& A, double tol, int max_it, int check_every, double* vec_lo, double* vec_hi,
@@ -777,7 +808,8 @@ struct PcOperator {
   ~PcOperator() { data.release(); }
 };
 // M: the mass matrix with CSR values (which == 2 only).  Refuses every pairing pph_preconditioned_extremes documents as invalid
-int pc_operator_prepare(pph_ctx* ctx, int which, int pc_type, int mg_smooth, const Csr* M, PcOperator* P);
+int pc_operator_prepare(pph_ctx* ctx, int which, int pc_type, int mg_smooth, const Csr* M, PcOperator* P,
+                        const char* fn = "pph_preconditioned_extremes");   // fn: the entry point named in the messages
 // z = B r, set to 0 on the constrained rows; r must be 0 there
 int pc_operator_apply(pph_ctx* ctx, const PcOperator& P, const double* r, double* z);
 // extreme eigenvalues of B A by Lanczos in the B inner product (pph_eig.hip; out as pph_preconditioned_extremes documents it)

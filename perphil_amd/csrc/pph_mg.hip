@@ -497,6 +497,7 @@ void mg_release(pph_ctx* ctx) {
   ctx->mg.clear();
   ctx->mg_w.release();
   for (int f = 0; f < 2; ++f) { ctx->mg_tail_pack[f].release(); ctx->mg_tail_lt[f] = -1; }
+  cmg_release(ctx);         // the coupled cycle's buffers follow the hierarchy's
   la_release_graphs(ctx);   // captured iteration bodies hold the hierarchy's pointers
   ctx->mg_epoch++;
   ctx->mg_ok = false;
@@ -536,6 +537,7 @@ static int mg_tail_pack(pph_ctx* ctx, int which);
 
 int mg_setup(pph_ctx* ctx) {
   if (ctx->mg_ok) return PPH_OK;
+  ctx->mg_values_epoch++;   // what follows the hierarchy's values (the coupled cycle's set-up, pph_cmg.hip) is out of date
   const bool build = !ctx->mg_struct_ok;  // level meshes / patterns / buffers survive re-assembly
   if (build) mg_release(ctx);
   const MeshData& fm = ctx->mesh;
@@ -1643,4 +1645,37 @@ void mg_vcycle(pph_ctx* ctx, int which, const double* rin, double* zout, int nsm
     if (l == 0 && timed) (void)hipEventRecord(ctx->pmg_ev[3], ctx->stream);
   }
   ctx->comm_suspended = false;
+}
+
+// ---- the hierarchy's products and transfers for one field, for the coupled cycle (pph_cmg.hip; single context) ----------
+Csr mg_level_csr(const pph_ctx* ctx, int l, int which) { return level_csr(ctx, ctx->mg[l], which); }
+
+// bc = R rf from level l to l + 1 with field `which`'s masks (0 on constrained coarse dofs)
+void mg_restrict_field(pph_ctx* ctx, int l, int which, const double* rf, double* bc) {
+  MgLevel& L = ctx->mg[l];
+  MgLevel& C = ctx->mg[l + 1];
+  if (ctx->mesh.kind == PPH_CELL_HEX)
+    hipLaunchKernelGGL(k_restrict_q1<3>, dim3(mg_grid(C.n)), dim3(256), 0, ctx->stream, bc, rf, C.maskp[which], L.maskp[which],
+                       tgeom(L, C), (double*)nullptr, (const double*)nullptr, (const double*)nullptr, C.rfast[which].p);
+  else if (ctx->mesh.kind == PPH_CELL_QUAD)
+    hipLaunchKernelGGL(k_restrict_q1<2>, dim3(mg_grid(C.n)), dim3(256), 0, ctx->stream, bc, rf, C.maskp[which], L.maskp[which],
+                       tgeom(L, C), (double*)nullptr, (const double*)nullptr, (const double*)nullptr, C.rfast[which].p);
+  else
+    hipLaunchKernelGGL(k_restrict, dim3(mg_grid(C.n)), dim3(256), 0, ctx->stream, bc, rf, make_transfer_stencil(ctx->mesh.kind),
+                       C.maskp[which], L.maskp[which], tgeom(L, C), (double*)nullptr, (const double*)nullptr,
+                       (const double*)nullptr);
+}
+
+// xf += P xc from level l + 1 to l, 0 on field `which`'s constrained fine dofs
+void mg_prolong_add_field(pph_ctx* ctx, int l, int which, double* xf, const double* xc) {
+  MgLevel& L = ctx->mg[l];
+  MgLevel& C = ctx->mg[l + 1];
+  const TGeom tg = tgeom(L, C);
+  const int kind = ctx->mesh.kind;
+  if (kind == PPH_CELL_QUAD || kind == PPH_CELL_HEX)
+    hipLaunchKernelGGL(k_prolong_add<0>, dim3(mg_grid(L.n)), dim3(256), 0, ctx->stream, xf, xc, L.maskp[which], tg);
+  else if (kind == PPH_CELL_TET)
+    hipLaunchKernelGGL(k_prolong_add<1>, dim3(mg_grid(L.n)), dim3(256), 0, ctx->stream, xf, xc, L.maskp[which], tg);
+  else
+    hipLaunchKernelGGL(k_prolong_add<2>, dim3(mg_grid(L.n)), dim3(256), 0, ctx->stream, xf, xc, L.maskp[which], tg);
 }

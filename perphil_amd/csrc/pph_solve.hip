@@ -737,7 +737,16 @@ static int validate_cfg(pph_ctx* ctx, const pph_solver_cfg* cfg) {
   PPH_REQUIRE(ctx, cfg != nullptr, "solver cfg is NULL");
   PPH_REQUIRE(ctx, cfg->ksp_type >= PPH_KSP_PREONLY && cfg->ksp_type <= PPH_KSP_GMRES, "unknown ksp_type %d",
               cfg->ksp_type);
-  PPH_REQUIRE(ctx, cfg->pc_type >= PPH_PC_NONE && cfg->pc_type <= PPH_PC_PMG, "unknown pc_type %d", cfg->pc_type);
+  PPH_REQUIRE(ctx, cfg->pc_type >= PPH_PC_NONE && cfg->pc_type <= PPH_PC_CMG, "unknown pc_type %d", cfg->pc_type);
+  // the coupled cycle preconditions the monolithic system, on one context with a CG-1 hierarchy
+  PPH_REQUIRE(ctx, cfg->inner_pc_type != PPH_PC_CMG || !(cfg->pc_type == PPH_PC_FIELDSPLIT || cfg->picard),
+              "pc_type pph_cmg is a cycle on the coupled system, not a block preconditioner: use it as pc_type of a monolithic solve");
+  if (cfg->pc_type == PPH_PC_CMG) {
+    PPH_REQUIRE(ctx, !cfg->picard, "pc_type pph_cmg preconditions the monolithic Krylov solve: not available with picard");
+    PPH_REQUIRE(ctx, ctx->mesh.degree == 1,
+                "pc_type pph_cmg runs on the CG-1 hierarchy: degree-2 spaces have none (a coupled pph_pmg does not exist)");
+    PPH_REQUIRE(ctx, ctx->world == 1, "pc_type pph_cmg: single context only (no slab decomposition)");
+  }
   PPH_REQUIRE(ctx, cfg->pc_type != PPH_PC_PMG, "pc_type pph_pmg applies to the scalar blocks: use it as inner_pc_type");
   // degree 2 has no multigrid hierarchy: pc mg, and block solves on it (which the LU blocks also stand for), are refused
   PPH_REQUIRE(ctx, ctx->mesh.degree == 1 || (cfg->pc_type != PPH_PC_MG &&
@@ -971,6 +980,13 @@ int pph_solve_device(pph_ctx* ctx, const pph_solver_cfg* cfg, pph_solve_info* in
       hipLaunchKernelGGL(k_block2_build, dim3(grid), dim3(256), 0, ctx->stream, ctx->mesh.rowptr.p, ctx->mesh.col.p,
                          ctx->A11.p, ctx->A22.p, ctx->A12.p, ctx->A21p(), n, binv);
       pc = [&, binv](const double* in, double* o) { la_block2_apply(ctx, o, binv, in, n); };
+    } else if (cfg->pc_type == PPH_PC_CMG) {
+      // one coupled multigrid cycle per application (pph_cmg.hip)
+      PPH_TRY(cmg_setup(ctx));
+      PPH_TRY(cmg_collect_failures(ctx));   // what an earlier application outside a solve left in the record is not this solve's
+      ctx->coarse_failed = 0;
+      const int ns = cfg->mg_smooth;
+      pc = [&, ns](const double* in, double* o) { if (cmg_apply(ctx, in, o, ns) < 0) bs.failed = true; };
     } else if (cfg->pc_type == PPH_PC_ILU) {
       // ILU(0) of the monolithic field-major CSR (GMRES_ILU_PARAMS, parameters.py:27)
       if (!ctx->ilu[0].valid) PPH_TRY(ilu_factor(ctx, ctx->ilu[0], A));
@@ -1004,6 +1020,7 @@ int pph_solve_device(pph_ctx* ctx, const pph_solver_cfg* cfg, pph_solve_info* in
       PPH_TRY(gmres_solve(ctx, Aop, N, ctx->rhs.p, du, pc, cfg->restart, cfg->rtol, cfg->atol, cfg->max_it, &ko, hist,
                           hist_cap, pph_owned_seg(A.geom, N)));
     }
+    if (cfg->pc_type == PPH_PC_CMG) PPH_TRY(cmg_collect_failures(ctx));   // coarsest solves on the device that stopped short
     inf.iterations = ko.its;
     inf.inner_iterations = bs.total_its;
     inf.resnorm = ko.res;
@@ -1109,8 +1126,7 @@ int pc_apply_device(pph_ctx* ctx, int which, int pc_type, int ns, const double* 
 // The block cases go through pc_apply_prepare / pc_apply_device; what pc_apply_device redoes per application (the Jacobi
 // diagonal) is taken once here.  The monolithic cases are those of pph_solve_device (Jacobi, 2 x 2 block-Jacobi, ILU(0) on
 // ctx->ilu[0]), with data of their own so that a later solve finds its work vectors untouched.
-int pc_operator_prepare(pph_ctx* ctx, int which, int pc_type, int mg_smooth, const Csr* M, PcOperator* P) {
-  const char* fn = "pph_preconditioned_extremes";
+int pc_operator_prepare(pph_ctx* ctx, int which, int pc_type, int mg_smooth, const Csr* M, PcOperator* P, const char* fn) {
   PPH_REQUIRE(ctx, ctx->world == 1, "%s works on a single context (the whole operator on one device)", fn);
   PPH_REQUIRE(ctx, which == 0 || (which >= 2 && which <= 4),
               "%s: which must be 0 (monolithic), 2 (M), 3 (A11) or 4 (A22), the symmetric positive definite operators; got %d", fn, which);
@@ -1140,11 +1156,14 @@ int pc_operator_prepare(pph_ctx* ctx, int which, int pc_type, int mg_smooth, con
     }
     P->mask[0] = ctx->bcmask[f].p;
   } else if (which == 0) {
-    PPH_REQUIRE(ctx, ctx->mono_ok, "monolithic CSR not assembled (pph_assemble_dpp(..., monolithic=1))");
-    PPH_REQUIRE(ctx, pc_type == PPH_PC_JACOBI || pc_type == PPH_PC_BLOCK2 || pc_type == PPH_PC_ILU,
-                "%s: pc_type %d is no symmetric preconditioner of the monolithic system (jacobi, pph_block2, ilu)", fn, pc_type);
+    PPH_REQUIRE(ctx, ctx->mono_ok, "%s: monolithic CSR not assembled (pph_assemble_dpp(..., monolithic=1))", fn);
+    PPH_REQUIRE(ctx, pc_type == PPH_PC_JACOBI || pc_type == PPH_PC_BLOCK2 || pc_type == PPH_PC_ILU || pc_type == PPH_PC_CMG,
+                "%s: pc_type %d is no symmetric preconditioner of the monolithic system (jacobi, pph_block2, ilu, pph_cmg)", fn, pc_type);
     const Csr A = mono_csr(ctx);
-    if (pc_type == PPH_PC_JACOBI) {
+    if (pc_type == PPH_PC_CMG) {
+      built = !(ctx->mg_ok && ctx->cmg_ok && ctx->cmg_epoch == ctx->mg_values_epoch);
+      PPH_TRY(cmg_setup(ctx));
+    } else if (pc_type == PPH_PC_JACOBI) {
       PPH_TRY(P->data.alloc(ctx, (size_t)(2 * n)));
       la_extract_diag_inv(ctx, A, P->data.p);
     } else if (pc_type == PPH_PC_BLOCK2) {
@@ -1179,6 +1198,7 @@ int pc_operator_apply(pph_ctx* ctx, const PcOperator& P, const double* r, double
     return PPH_OK;   // (r is 0 on the constrained rows, so is z)
   }
   if (P.which == 0) {
+    if (P.pc_type == PPH_PC_CMG) return cmg_apply(ctx, r, z, P.ns);   // (0 on the constrained rows by construction)
     if (P.pc_type == PPH_PC_BLOCK2) la_block2_apply(ctx, z, P.data.p, r, n);
     else PPH_REQUIRE(ctx, ilu_apply(ctx, ctx->ilu[0], r, z) >= 0, "pph_preconditioned_extremes: ILU(0) application failed");
     pmg_zero_masked(ctx, z, P.mask[0], n);
@@ -1209,6 +1229,66 @@ int pph_pc_apply(pph_ctx* ctx, int which, int pc_type, int mg_smooth, const doub
   PPH_HIP(ctx, hipGetLastError());
   r.release(); z.release(); w.release();
   return st;
+}
+
+// ---- one monolithic preconditioner, applied to a caller's vector of 2n (parity checks of the coupled cycle itself) -------
+int pph_pc_apply_coupled(pph_ctx* ctx, int pc_type, int mg_smooth, const double* r_host, double* z_host) {
+  if (!ctx) return PPH_ERR_INVALID;
+  PPH_REQUIRE(ctx, r_host && z_host, "NULL vector");
+  PPH_REQUIRE(ctx, ctx->asm_ok, "pph_pc_apply_coupled before pph_assemble_dpp");
+  PPH_REQUIRE(ctx, pc_type == PPH_PC_CMG || pc_type == PPH_PC_BLOCK2 || pc_type == PPH_PC_JACOBI,
+              "pph_pc_apply_coupled: pc_type %d is no preconditioner of the coupled system applied here (pph_cmg, pph_block2, jacobi)",
+              pc_type);
+  PcOperator P;
+  PPH_TRY(pc_operator_prepare(ctx, 0, pc_type, mg_smooth, nullptr, &P, "pph_pc_apply_coupled"));
+  const int64_t n = ctx->n, N = 2 * n;
+  DevBuf<double> r, z;
+  PPH_TRY(r.alloc(ctx, (size_t)N));
+  PPH_TRY(z.alloc(ctx, (size_t)N));
+  PPH_HIP(ctx, hipMemcpyAsync(r.p, r_host, sizeof(double) * (size_t)N, hipMemcpyHostToDevice, ctx->stream));
+  pmg_zero_masked(ctx, r.p, ctx->bcmask[0].p, n);   // as the residuals of the Krylov loops: 0 on constrained rows
+  pmg_zero_masked(ctx, r.p + n, ctx->bcmask[1].p, n);
+  const int st = pc_operator_apply(ctx, P, r.p, z.p);
+  if (pc_type == PPH_PC_CMG) PPH_TRY(cmg_collect_failures(ctx));   // (this entry point has nobody to report them to: the record is cleared)
+  if (st == PPH_OK) PPH_HIP(ctx, hipMemcpyAsync(z_host, z.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, ctx->stream));
+  PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  PPH_HIP(ctx, hipGetLastError());
+  r.release(); z.release();
+  return st;
+}
+
+// diagnostic (tools/cmg_probe.py): `reps` coupled cycles on a vector of ones, then `reps` fine-level smoothing passes of the
+// row-walk kernel alone (without the products of the diagonal blocks before it), each series timed with one event pair
+int pph_cmg_bench(pph_ctx* ctx, int mg_smooth, int reps, double* out4) {
+  if (!ctx) return PPH_ERR_INVALID;
+  PPH_REQUIRE(ctx, out4 && reps >= 1, "pph_cmg_bench: needs reps >= 1 and an output array");
+  PPH_REQUIRE(ctx, ctx->asm_ok && ctx->mono_ok, "pph_cmg_bench: needs the monolithic assembly");
+  PPH_HIP(ctx, hipSetDevice(ctx->device));
+  PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const auto t0 = std::chrono::steady_clock::now();
+  PPH_TRY(cmg_setup(ctx));
+  const int64_t n = ctx->n, N = 2 * n;
+  const int ns = mg_smooth > 0 ? mg_smooth : 2;
+  DevBuf<double> r, z;
+  PPH_TRY(r.alloc(ctx, (size_t)N));
+  PPH_TRY(z.alloc(ctx, (size_t)N));
+  la_set(ctx, r.p, 1.0, N);
+  PPH_TRY(cmg_apply(ctx, r.p, z.p, ns));   // warm-up
+  PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  out4[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  float ms = 0.f;
+  PPH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  for (int i = 0; i < reps; ++i) PPH_TRY(cmg_apply(ctx, r.p, z.p, ns));
+  PPH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  PPH_HIP(ctx, hipEventSynchronize(ctx->ev1));
+  PPH_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  out4[0] = (double)ms / reps;
+  out4[2] = cmg_step_bytes(ctx);
+  PPH_TRY(cmg_step_bench(ctx, reps, &out4[1]));
+  PPH_TRY(cmg_collect_failures(ctx));
+  r.release(); z.release();
+  PPH_HIP(ctx, hipGetLastError());
+  return PPH_OK;
 }
 
 // diagnostic (tools/pmg_probe.py): `reps` applications of the block preconditioner to a vector of ones.

@@ -83,6 +83,16 @@ def params_for(approach: Approach) -> Dict:
     raise ValueError(f"Unknown approach: {approach}")
 
 
+def default_configurations() -> List[Tuple[str, Dict]]:
+    """(label, options) of the reference's approaches: what a study runs when nothing is opted into."""
+    return [(a.value, params_for(a)) for a in Approach]
+
+
+def cmg_configurations() -> List[Tuple[str, Dict]]:
+    """Opt-in (no reference counterpart): CG on the monolithic system under the coupled multigrid cycle pph_cmg."""
+    return [("CG + coupled MG", solver_params.CG_CMG_PARAMS.copy())]
+
+
 def solve_on_mesh(W, approach: Approach, params: Optional[DPPParameters] = None,
                   bcs: Optional[List[fd.DirichletBC]] = None) -> SolveResult:
     from .solver import solve_dpp, solve_dpp_nonlinear

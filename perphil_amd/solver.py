@@ -21,6 +21,10 @@ pc_type ilu (pc_factor_levels 0)        ILU(0) in the natural row order, factori
                                         level-scheduled on the device (levels i + 2j + 4k of the lexicographic
                                         numbering), monolithic system or field-split / Picard blocks;
                                         block ksp_type gmres = restarted GMRES(30) on the block
+pc_type pph_cmg                         coupled multigrid on the monolithic system (ksp_type cg | gmres | preonly): one
+                                        symmetric V-cycle over the CG-1 hierarchy whose Chebyshev smoother inverts the
+                                        2 x 2 block of the two pressures of every node; pph_mg_smooth steps per level
+                                        side (default 2).  Degree 1, one device; not a fieldsplit block pc
 snes_type ngs | nrichardson             block Picard (fixed-stress) sweeps per dpp_delayed_form
                                         (dpp.py:196-203); the reference's PETSc secant-NGS history is
                                         not reproduced, the fixed point is
@@ -86,6 +90,9 @@ def _inner_cfg(cfg: _ffi.SolverCfg, subs: List[Dict], notes: List[str]) -> None:
         cfg.inner_exact = 1      # (blocks of at most 4096 rows: one on-chip solve per block instead of a host-driven loop)
         notes.append("block LU -> CG + geometric multigrid, rtol 1e-12 (blocks of <= 4096 rows: one on-chip Jacobi-CG solve)")
         return
+    if p == "pph_cmg":
+        raise NotImplementedError("pc_type 'pph_cmg' is a cycle on the coupled system, not a fieldsplit block pc: use it as the "
+                                  "top-level pc_type of a cg / gmres solve")
     if p not in ("mg", "pph_pmg", "jacobi", "none", "ilu"):
         raise NotImplementedError(f"fieldsplit block pc_type {p!r} is not supported (lu, ilu, mg, pph_pmg, jacobi, none)")
     # pph_pmg: the space's own operator on top of the CG-1 multigrid hierarchy of the same cells (degree 2; at degree 1 it is mg)
@@ -175,7 +182,7 @@ def translate_options(params: Dict, nonlinear: bool = False) -> Tuple[_ffi.Solve
     if pc in ("lu", "cholesky"):
         raise NotImplementedError("pc_type lu is only supported with ksp_type preonly (direct-equivalent solve)")
     table = {"none": _ffi.PC_NONE, "jacobi": _ffi.PC_JACOBI, "pph_block2": _ffi.PC_BLOCK2,
-             "fieldsplit": _ffi.PC_FIELDSPLIT, "ilu": _ffi.PC_ILU}
+             "fieldsplit": _ffi.PC_FIELDSPLIT, "ilu": _ffi.PC_ILU, "pph_cmg": _ffi.PC_CMG}
     if pc not in table:
         raise NotImplementedError(f"pc_type {pc!r} is not supported")
     cfg.pc_type = table[pc]
@@ -210,6 +217,8 @@ def degree2_unsupported(cfg: _ffi.SolverCfg, info: dict) -> Optional[str]:
         return "ksp_type preonly + pc_type lu runs as field-split GMRES with multigrid-CG block solves"
     if cfg.pc_type == _ffi.PC_MG:
         return "pc_type mg needs the multigrid hierarchy"
+    if cfg.pc_type == _ffi.PC_CMG and not cfg.picard:
+        return "pc_type pph_cmg is a cycle on the CG-1 multigrid hierarchy"
     if (cfg.pc_type == _ffi.PC_FIELDSPLIT or cfg.picard) and cfg.inner_pc_type == _ffi.PC_MG:
         what = "Picard" if cfg.picard else "field-split"
         if cfg.inner_exact:
@@ -236,6 +245,10 @@ def _run(W, model_params: DPPParameters, bcs, solver_parameters: Dict, nonlinear
             raise NotImplementedError("degree-2 spaces are not distributed: build the mesh with comm=fd.COMM_SELF")
         ctx = mesh.context(device, degree=degree)
     else:
+        if cfg.pc_type == _ffi.PC_CMG and not cfg.picard and mesh.distributed:
+            # (before the context exists, like the degree-2 refusals)
+            raise NotImplementedError("pc_type pph_cmg runs on one device: not available on a distributed mesh (build the "
+                                      "mesh with comm=fd.COMM_SELF)")
         # this rank's slab + its transport when the mesh is distributed (fd.Mesh); the solver loops are the same
         ctx = mesh.context(device)
     if mesh.distributed:

@@ -103,3 +103,9 @@ PICARD_PMG_SOLVER_PARAMS: dict = {
     "fieldsplit_0": {"ksp_type": "cg", "pc_type": "pph_pmg", "ksp_rtol": 1e-10},
     "fieldsplit_1": {"ksp_type": "cg", "pc_type": "pph_pmg", "ksp_rtol": 1e-10},
 }
+# coupled multigrid on the monolithic system (pc_type pph_cmg): one V-cycle whose smoother inverts the 2 x 2 block of the
+# two pressures of every node, so the exchange term is resolved on every level - the preset for beta / mu large against
+# the weaker network's diffusion, where the sweeps and the field split above stall
+CG_CMG_PARAMS: dict = {"ksp_type": "cg", "pc_type": "pph_cmg", "ksp_rtol": 1.0e-8, "ksp_atol": 1.0e-12,
+                       "ksp_max_it": _MAX_ITERATION_NUMBER}
+GMRES_CMG_PARAMS: dict = {"pc_type": "pph_cmg", **GMRES_PARAMS}
