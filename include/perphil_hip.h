@@ -474,7 +474,10 @@ int pph_comm_times(pph_ctx* ctx, double* out4);
  * out[32] 1 when the last assembly did not store the operator entries of the fine level's straight-line rows (option
  * "asm_store_values" 0), out[33] launches that wrote such rows because a reader asked, since the context was created,
  * out[34] levels whose row dictionary was refused on the device while their rows were left out - written by the repair launch
- * behind that assembly's last check kernel, counted when the solve's end retires the dictionary. */
+ * behind that assembly's last check kernel, counted when the solve's end retires the dictionary;
+ * out[35] product launches of the last solve (or pph_pc_apply) whose smoothing epilogue took its factors 1 / a_ii from a row
+ * dictionary's table of inverse diagonals instead of the dinv array (option "sell_dict_dinv"; launches recorded into a
+ * captured graph count once, when recorded). */
 int pph_get_timers(pph_ctx* ctx, double* out, int n);
 /* tuning / profiling switches (no reference counterpart; defaults in brackets):
  *   "op_format" [1]      operator format of the scalar blocks inside block solves / Picard sweeps: 1 stencil-ELL
@@ -545,7 +548,13 @@ int pph_get_timers(pph_ctx* ctx, double* out, int n);
  *                        products on hexahedra keep the x window in registers (k_spmv_dict_walk), "sell_dict_blocks"
  *                        [1024] their grid, "sell_dict_zconst" [1]: where the class of an in-plane position is the same on all
  *                        interior planes (verified on the class array at the build) a step takes its classes from the step
- *                        below instead of loading them; 0 takes effect at once, 1 at the next assembly
+ *                        below instead of loading them; 0 takes effect at once, 1 at the next assembly.
+ *                        "sell_dict_dinv" [1] (0 or 1, anything else is refused): the Jacobi-type epilogues of dictionary
+ *                        products (the cycle's smoothing products; the Picard sweeps' coupling products that write the next
+ *                        solve's first guess) take 1 / a_ii from a table with one entry per class - the class's diagonal entry
+ *                        through the assembly's expression, so the same double - instead of streaming the n-entry array;
+ *                        coupling products read the class of the DIAGONAL block's dictionary for that.  A dictionary refused
+ *                        on the device, no dictionary, slabs: the array as before.  Takes effect at the next launch
  *   "fold_finals" [1]    single context: the final reductions of p.Ap and of the multigrid cycle's r.z are summed inside the
  *                        kernels that consume them instead of by launches of their own (same sums, same order)
  *   "pmg_fused" [1]      PPH_PC_PMG at degree 2: the smoother steps and residuals of the degree-2 level run in the tile kernels

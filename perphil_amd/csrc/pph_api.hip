@@ -799,6 +799,13 @@ int pph_set_option(pph_ctx* ctx, const char* name, double value) {
     return PPH_OK;
   }
   if (!strcmp(name, "sell_dict_zconst")) { ctx->sell_dict_zconst = value != 0; la_release_graphs(ctx); return PPH_OK; }
+  if (!strcmp(name, "sell_dict_dinv")) {   // takes effect at the next product launch
+    PPH_REQUIRE(ctx, value == 0.0 || value == 1.0, "sell_dict_dinv: 0 the dinv arrays are read, 1 inverse diagonals from the row classes (got %g)", value);
+    ctx->sell_dict_dinv = (int)value;
+    ctx->n_dict_dinv = 0;
+    la_release_graphs(ctx);
+    return PPH_OK;
+  }
   if (!strcmp(name, "sell_dict_poison")) {
     // tests: mark the dictionaries of the fine blocks as failed ON THE DEVICE only, as a failed re-assembly check would -
     // the products launched for them must then take the stored values (the plain path inside the dictionary kernel)
@@ -918,7 +925,7 @@ int pph_get_timers(pph_ctx* ctx, double* out, int n) {
     (void)hipMemcpyAsync(dst, ctx->D11.state.p, sizeof(dst), hipMemcpyDeviceToHost, ctx->stream);
     (void)hipStreamSynchronize(ctx->stream);
   }
-  const double v[35] = {ctx->t_mesh, ctx->t_asm, ctx->t_bc, ctx->t_solve,
+  const double v[36] = {ctx->t_mesh, ctx->t_asm, ctx->t_bc, ctx->t_solve,
                         ctx->t_spmv[0], (double)ctx->n_spmv[0], ctx->spmv_bytes[0],
                         ctx->t_spmv[1], (double)ctx->n_spmv[1], ctx->spmv_bytes[1], (double)ctx->n_halo,
                         ctx->t_spmv_fine, (double)ctx->n_spmv_fine, ctx->spmv_bytes_fine, (double)ctx->n_split,
@@ -928,8 +935,9 @@ int pph_get_timers(pph_ctx* ctx, double* out, int n) {
                         ctx->asm_rows_win, ctx->asm_rows_gen, ctx->asm_rows_all,
                         (double)ctx->onchip_solves, (double)ctx->onchip_unconverged, (double)ctx->onchip_its,
                         (double)ctx->n_presmooth_skipped, (double)ctx->n_presmooth_late, (double)ctx->n_presmooth_unused,
-                        ctx->vals0.stale ? 1.0 : 0.0, (double)ctx->n_values_materialized, (double)ctx->n_store_repairs};
-  for (int i = 0; i < n && i < 35; ++i) out[i] = v[i];
+                        ctx->vals0.stale ? 1.0 : 0.0, (double)ctx->n_values_materialized, (double)ctx->n_store_repairs,
+                        (double)ctx->n_dict_dinv};
+  for (int i = 0; i < n && i < 36; ++i) out[i] = v[i];
   return PPH_OK;
 }
 

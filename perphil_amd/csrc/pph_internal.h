@@ -83,6 +83,7 @@ struct SellDict {
   DevBuf<int64_t> rep;               // [PPH_DICT_HASH] a row of the class that won hash slot h; [PPH_DICT_HASH + c]: of class c
   DevBuf<uint16_t> map;              // [PPH_DICT_HASH] hash slot -> class
   DevBuf<double> tab;                // [PPH_DICT_CAP][S]
+  DevBuf<double> inv;                // [PPH_DICT_CAP] (d != 0.0) ? 1.0 / d : 1.0 of the class's diagonal entry d: the row's dinv as the assembly forms it; written wherever tab is
   DevBuf<int> state;                 // [0] classes  [1] 1 usable / 0 not built / < 0 refused  (read by every product launch)  [2] k_dict_zconst's count
   int ncls = 0;                      // host copy of state[0] after the build
   bool on = false;                   // products use the dictionary
@@ -97,7 +98,7 @@ struct SellDict {
   DevBuf<int32_t> src;               // [ncls][S]: where tab[c][s] comes from in the group's mini operator (-1: the 0 outside [0, n))
   bool adj_ok = false;
   bool checked = false;              // this assembly's rows were checked by the assembly kernel itself
-  void release() { cls.release(); keys.release(); rep.release(); map.release(); tab.release(); state.release(); adj.release(); src.release(); ncls = 0; on = tried = adj_ok = checked = zconst = false; n = 0; val = nullptr; }
+  void release() { cls.release(); keys.release(); rep.release(); map.release(); tab.release(); inv.release(); state.release(); adj.release(); src.release(); ncls = 0; on = tried = adj_ok = checked = zconst = false; n = 0; val = nullptr; }
 };
 #define PPH_DICT_ADJW (PPH_DICT_CAP / 32 + 1)
 #define PPH_DICT_FUSE_CAP 128      // classes per operator up to which the assembly kernel holds the stored halves of the tables in LDS
@@ -577,6 +578,8 @@ struct pph_ctx {
   int64_t sell_dict_min_rows = 1000000; // ... of operators with at least this many rows
   int sell_dict_blocks = 1024, sell_dict_zwalk = -1;   // grid (cap) of a dictionary product; chunk z-walk of k_spmv_sell<DICT> (-1: as sell_zwalk)
   int sell_dict_zconst = 1;             // ... without class loads where the classes are constant along z (SellDict::zconst)
+  int sell_dict_dinv = 1;               // ... whose smoothing epilogues take 1 / a_ii from the classes' table (SellDict::inv), not from the dinv stream
+  int64_t n_dict_dinv = 0;              // product launches that did, since the last solve or preconditioner application began (pph_get_timers out[35])
   int sell_dict_walk = 1;               // whole-operator dictionary products of hexahedral blocks: x window in registers (k_spmv_dict_walk)
   int sell_dict_cap = PPH_DICT_CAP;     // classes accepted (tests lower it to force the plain path)
   int sell_rpt = 2, sell_blocks = 0, sell_group = 0;   // SELL SpMV tuning: rows per thread, grid cap, XCD chunk group
@@ -640,12 +643,14 @@ void la_spmv_resid(pph_ctx* ctx, const Csr& A, const double* x, const double* b,
 // b, -1 without: the Picard sweeps' coupling product + residual bookkeeping + norm in one pass; `tmp`: n doubles,
 // used when A has no stencil-ELL copy)
 // z0 != null (stencil-ELL operators): also z0 = dinv0 .* R * (*w0), the first pre-smoothing of the solve that starts from R
+// dinv_dict (both): the row dictionary of the operator whose 1 / a_ii the dinv array holds, if the caller knows one (null: the
+// array is read) - the product may take the factors from that dictionary's table of inverse diagonals instead (sell_dinv_table)
 void la_spmv_shift(pph_ctx* ctx, const Csr& A, const double* x, const double* b, double* R, double* told, double* tmp,
                    int slot, int64_t dlo, int64_t dhi, double* z0 = nullptr, const double* dinv0 = nullptr,
-                   const double* w0 = nullptr);
+                   const double* w0 = nullptr, const SellDict* dinv_dict = nullptr);
 void la_spmv_jacobi(pph_ctx* ctx, const Csr& A, const double* x, const double* b, const double* dinv,
                     const double* w /* device */, double* y, int dot_slot = -1, int64_t dlo = 0, int64_t dhi = 0,
-                    bool x_ghosts_valid = false);
+                    bool x_ghosts_valid = false, const SellDict* dinv_dict = nullptr);
 // y = A x and partial sums of dot(x, y) -> scal slot
 // (copy_src >= 0: scal[copy_dst] = scal[copy_src] is done by the final reduction's single workgroup)
 // defer: the final reduction of the partial sums is left pending for the kernel that consumes the scalar (la_cg_update_dev;
@@ -711,7 +716,12 @@ void la_reset_spmv_stats(pph_ctx* ctx);
 // stencil-ELL operator format (pph_sell.hip)
 int sell_spmv(pph_ctx* ctx, const Sell& E, int64_t n, int mode, const double* x, const double* b, const double* dinv,
               const double* w /* device */, double* y, double* part, int64_t dlo = 0, int64_t dhi = 0, double* aux = nullptr, double* z0 = nullptr,
-              int64_t cbeg = 0, int64_t cend = -1, int grid_cap = 0);
+              int64_t cbeg = 0, int64_t cend = -1, int grid_cap = 0, const SellDict* dinv_dict = nullptr);
+// Whether that launch (whole operator: cend < 0) takes the factors 1 / a_ii of its epilogue from the table of inverse diagonals
+// of `dd`, the dictionary of the operator whose diagonal `dinv` inverts, and issues no dinv load.  Modes 3 / 4: dd is the
+// product operator's own usable dictionary.  Modes 5 / 6 with z0: dd is usable, describes the same box, and - where the walk
+// kernel takes the product's classes from the plane below - is constant along z as well.  Option sell_dict_dinv 0: never.
+bool sell_dinv_table(const pph_ctx* ctx, const Sell& E, int64_t n, int mode, bool has_z0, const SellDict* dd);
 #ifdef __HIPCC__
 // two consecutive rows' entries of a vector as ONE 16-byte access per lane (8-byte alignment is enough for the hardware):
 // a wave then touches 1 KB of consecutive bytes per instruction - with one 8-byte store per row, each of the two store
@@ -772,8 +782,9 @@ void mg_onchip_cg(pph_ctx* ctx, const Sell& E, const double* dinv, const double*
 void mg_release(pph_ctx* ctx);
 // z = Vcycle(r) for block `which` (0: A11, 1: A22); r and z have fine-level length n
 void mg_vcycle(pph_ctx* ctx, int which, const double* r, double* z, int nsmooth);
+// (dinv_dict: the fine level operator's row dictionary while usable - *dinv is that operator's 1 / a_ii)
 bool mg_pre_smoother(pph_ctx* ctx, int which, int nsmooth, const double** dinv, const double** w /* device */,
-                     bool* launch_only);
+                     bool* launch_only, const SellDict** dinv_dict = nullptr);
 
 // the hierarchy's products and transfers for one field (single context): what the coupled cycle is composed of
 Csr mg_level_csr(const pph_ctx* ctx, int l, int which);

@@ -224,10 +224,10 @@ static int stream_T(int max_row) {
 // communication stream WHILE the interior rows are computed: x is complete at ev_x; the exchange waits for ev_x
 // only, the boundary launches wait for the exchange (ev_h).  The rows' results do not depend on the split; the
 // partial sums of the dot-product modes are laid out launch after launch, so modes 1 and 2 are bit-identical.
-// Returns the number of partial sums written.
+// Returns the number of partial sums written.  dinv_dict: see la_spmv_jacobi (the split launches read the dinv array).
 static int sell_product(pph_ctx* ctx, const Csr& A, int mode, const double* x, const double* b, const double* dinv,
                         const double* w, double* y, double* part, int64_t dlo, int64_t dhi, double* aux, double* z0,
-                        bool need_halo) {
+                        bool need_halo, const SellDict* dinv_dict = nullptr) {
   const MeshData* g = A.geom;
   const bool ghosts = g && ctx->world > 1 && (g->glo || g->ghi) && need_halo;
   const bool one_field = g && A.nrows == g->n;
@@ -284,7 +284,7 @@ static int sell_product(pph_ctx* ctx, const Csr& A, int mode, const double* x, c
     (void)la_halo(ctx, *g, const_cast<double*>(x));
     if (A.nrows == 2 * g->n) (void)la_halo(ctx, *g, const_cast<double*>(x) + g->n);
   }
-  return sell_spmv(ctx, A.ell, A.nrows, mode, x, b, dinv, w, y, part, dlo, dhi, aux, z0);
+  return sell_spmv(ctx, A.ell, A.nrows, mode, x, b, dinv, w, y, part, dlo, dhi, aux, z0, 0, -1, 0, dinv_dict);
 }
 
 // returns the grid used (number of partial sums written when DOT)
@@ -292,7 +292,7 @@ static int sell_product(pph_ctx* ctx, const Csr& A, int mode, const double* x, c
 template <bool DOT>
 static int spmv_dispatch(pph_ctx* ctx, const Csr& A, const double* x, const double* bvec, double* y, double* part,
                          const double* jdinv = nullptr, const double* jw = nullptr, bool jdot = false, int64_t dlo = 0,
-                         int64_t dhi = 0, bool x_ghosts_valid = false) {
+                         int64_t dhi = 0, bool x_ghosts_valid = false, const SellDict* jdict = nullptr) {
   const int variant = DOT ? 1 : 0;
   if (A.geom && !x_ghosts_valid && !A.ell.val) {  // ghost planes of x <- owners (slabs only); field-major mixed vectors carry two fields
     (void)la_halo(ctx, *A.geom, const_cast<double*>(x));
@@ -316,12 +316,14 @@ static int spmv_dispatch(pph_ctx* ctx, const Csr& A, const double* x, const doub
   double bytes_per_nnz = 12.0;
   if (A.ell.val) {
     // stencil-ELL copy of the operator (pph_sell.hip): 8 B per stored entry, no index arrays
+    const int64_t t0 = ctx->n_dict_dinv;
     grid = sell_product(ctx, A, jdinv ? (jdot ? 4 : 3) : (DOT ? (bvec ? 7 : 2) : (bvec ? 1 : 0)), x, bvec, jdinv, jw, y,
-                        part ? part : partials(ctx), dlo, dhi, nullptr, nullptr, !x_ghosts_valid);
+                        part ? part : partials(ctx), dlo, dhi, nullptr, nullptr, !x_ghosts_valid, jdict);
     if (ev) (void)hipEventRecord(ev->e1, ctx->stream);
     // algorithmic bytes: every stored value once, x read once, y written once, plus the epilogue's vectors
-    // (b for the residual form; b and 1 / a_ii for the Jacobi update)
-    const double extra = jdinv ? 16.0 : (bvec ? 8.0 : 0.0);
+    // (b for the residual form; b and 1 / a_ii for the Jacobi update - without 1 / a_ii where the launch took it from the
+    // dictionary's table of inverse diagonals, sell_dinv_table)
+    const double extra = jdinv ? (ctx->n_dict_dinv != t0 ? 8.0 : 16.0) : (bvec ? 8.0 : 0.0);
     const double bytes = (sell_stream_bytes(ctx, A.ell) + 16.0 + extra) * (double)A.nrows;
     ctx->n_spmv[variant]++;
     ctx->spmv_bytes[variant] += bytes;
@@ -402,6 +404,7 @@ void la_reset_spmv_stats(pph_ctx* ctx) {
   la_harvest_spmv_times(ctx);
   for (int v = 0; v < 2; ++v) { ctx->t_spmv[v] = 0; ctx->spmv_bytes[v] = 0; ctx->n_spmv[v] = 0; }
   ctx->t_spmv_fine = 0; ctx->spmv_bytes_fine = 0; ctx->n_spmv_fine = 0;
+  ctx->n_dict_dinv = 0;
   ctx->t_comm[0] = ctx->t_comm[1] = 0; ctx->n_comm_timed[0] = ctx->n_comm_timed[1] = 0;
 }
 
@@ -418,9 +421,9 @@ void la_spmv_resid(pph_ctx* ctx, const Csr& A, const double* x, const double* b,
 // y = x + w * dinv .* (b - A x): one damped-Jacobi (one-step Chebyshev) sweep, out of place (y != x); A must carry a
 // stencil-ELL copy
 void la_spmv_jacobi(pph_ctx* ctx, const Csr& A, const double* x, const double* b, const double* dinv, const double* w,
-                    double* y, int dot_slot, int64_t dlo, int64_t dhi, bool x_ghosts_valid) {
+                    double* y, int dot_slot, int64_t dlo, int64_t dhi, bool x_ghosts_valid, const SellDict* dinv_dict) {
   const int grid = spmv_dispatch<false>(ctx, A, x, b, y, dot_slot >= 0 ? partials(ctx) : nullptr, dinv, w, dot_slot >= 0,
-                                        dlo, dhi, x_ghosts_valid);
+                                        dlo, dhi, x_ghosts_valid, dinv_dict);
   if (dot_slot >= 0) {
     if (ctx->defer_next_final && la_can_fold(ctx)) {
       ctx->defer_next_final = false;
@@ -433,7 +436,8 @@ void la_spmv_jacobi(pph_ctx* ctx, const Csr& A, const double* x, const double* b
 }
 
 void la_spmv_shift(pph_ctx* ctx, const Csr& A, const double* x, const double* b, double* R, double* told, double* tmp,
-                   int slot, int64_t dlo, int64_t dhi, double* z0, const double* dinv0, const double* w0) {
+                   int slot, int64_t dlo, int64_t dhi, double* z0, const double* dinv0, const double* w0,
+                   const SellDict* dinv_dict) {
   if (!A.ell.val) {   // (callers offer z0 only for stencil-ELL operators)
     if (b) la_spmv_resid(ctx, A, x, b, tmp); else la_spmv(ctx, A, x, tmp);
     la_shift(ctx, R, told, tmp, b ? 1.0 : -1.0, A.nrows);
@@ -455,9 +459,14 @@ void la_spmv_shift(pph_ctx* ctx, const Csr& A, const double* x, const double* b,
       (void)hipEventRecord(ev->e0, ctx->stream);
     }
   }
-  const int grid = sell_product(ctx, A, b ? 5 : 6, x, b, z0 ? dinv0 : nullptr, z0 ? w0 : nullptr, told, part, dlo, dhi, R, z0, true);
+  const int64_t t0 = ctx->n_dict_dinv;
+  const int grid = sell_product(ctx, A, b ? 5 : 6, x, b, z0 ? dinv0 : nullptr, z0 ? w0 : nullptr, told, part, dlo, dhi, R, z0, true,
+                                z0 ? dinv_dict : nullptr);
   if (ev) (void)hipEventRecord(ev->e1, ctx->stream);
-  const double bytes = (sell_stream_bytes(ctx, A.ell) + 16.0 + (b ? 8.0 : 0.0) + 24.0 + (z0 ? 16.0 : 0.0)) * (double)A.nrows;
+  // (z0: its store and the dinv0 stream - or, where the launch took 1 / a_ii from the second dictionary's table, the 2-byte classes
+  // of that dictionary, read as the product's own are: sell_stream_bytes)
+  const double dbytes = ctx->n_dict_dinv != t0 ? sell_stream_bytes(ctx, A.ell) : 8.0;
+  const double bytes = (sell_stream_bytes(ctx, A.ell) + 16.0 + (b ? 8.0 : 0.0) + 24.0 + (z0 ? 8.0 + dbytes : 0.0)) * (double)A.nrows;
   ctx->n_spmv[0]++;
   ctx->spmv_bytes[0] += bytes;
   if (A.nrows >= ctx->mesh.n) { ctx->n_spmv_fine++; ctx->spmv_bytes_fine += bytes; }

@@ -1534,12 +1534,14 @@ static void mg_vcycle_fused(pph_ctx* ctx, int which, const double* rin, double* 
       hipLaunchKernelGGL(k_prolong_to<2>, dim3(mg_grid(L.n)), dim3(256), 0, ctx->stream, L.t.p, x, C.x.p, L.maskp[which], tg);
     // ghost planes of L.t: x's were refreshed by the residual product of the downward leg, the coarse correction's
     // just above, and k_prolong_to interpolates ghost rows as well - one exchange per level and cycle less
+    // (L.dinv is 1 / a_ii of this level's own operator: with a usable row dictionary the product takes it from the classes)
     if (l == 0 && dot_slot >= 0) {
       la_spmv_jacobi(ctx, level_csr(ctx, L, which), L.t.p, b, L.dinv[which].p, cheb_wp(ctx, l, which), x, dot_slot,
-                     ctx->mg_dot_seg.off1, ctx->mg_dot_seg.off1 + ctx->mg_dot_seg.len1, true);
+                     ctx->mg_dot_seg.off1, ctx->mg_dot_seg.off1 + ctx->mg_dot_seg.len1, true, L.ell[which].dict);
       ctx->mg_dot_slot = -2;   // delivered
     } else {
-      la_spmv_jacobi(ctx, level_csr(ctx, L, which), L.t.p, b, L.dinv[which].p, cheb_wp(ctx, l, which), x, -1, 0, 0, true);
+      la_spmv_jacobi(ctx, level_csr(ctx, L, which), L.t.p, b, L.dinv[which].p, cheb_wp(ctx, l, which), x, -1, 0, 0, true,
+                     L.ell[which].dict);
     }
   }
   ctx->comm_suspended = false;
@@ -1547,9 +1549,11 @@ static void mg_vcycle_fused(pph_ctx* ctx, int which, const double* rin, double* 
 
 // the pre-smoothing the fused cycle starts with on the fine level: z0 = dinv .* r * w (false: the cycle is not the
 // fused one, nothing to offer)
-bool mg_pre_smoother(pph_ctx* ctx, int which, int nsmooth, const double** dinv, const double** w, bool* launch_only) {
+bool mg_pre_smoother(pph_ctx* ctx, int which, int nsmooth, const double** dinv, const double** w, bool* launch_only,
+                     const SellDict** dinv_dict) {
   if (!ctx->mg_ok || !mg_can_fuse(ctx, which, nsmooth)) return false;
   *dinv = ctx->mg[0].dinv[which].p;
+  if (dinv_dict) *dinv_dict = ctx->mg[0].ell[which].dict;
   *w = cheb_wp(ctx, 0, which);
   // the cycle consists of kernel launches only (capturable into a graph) unless its coarsest solve is host-driven
   const MgLevel& C = ctx->mg.back();

@@ -21,7 +21,8 @@ __device__ inline double sell_wave_sum(double v) {
 }
 
 // operands of the epilogue of a row block: requested before the matrix stream, not after the sums
-template <int MODE, int RPT, bool CLAMP>
+// TINV: dv comes from a dictionary's table of inverse diagonals (sell_rows), no dinv load
+template <int MODE, int RPT, bool CLAMP, bool TINV = false>
 __device__ __forceinline__ void sell_prologue(const double* __restrict__ x, const double* __restrict__ b,
                                               const double* __restrict__ dinv, const double* __restrict__ y,
                                               const double* __restrict__ aux, const double* __restrict__ z0, int64_t n,
@@ -32,8 +33,8 @@ __device__ __forceinline__ void sell_prologue(const double* __restrict__ x, cons
     act[0] = act[1] = true;
     if (MODE == 1 || (MODE >= 3 && MODE <= 5) || MODE == 7) sell_ld2(b + r0, bv[0], bv[1]);
     if ((MODE >= 2 && MODE <= 4) || MODE == 7) sell_ld2(x + r0, xr[0], xr[1]);
-    if (MODE == 3 || MODE == 4) sell_ld2(dinv + r0, dv[0], dv[1]);
-    if (MODE == 5 || MODE == 6) { sell_ld2(y + r0, tv[0], tv[1]); sell_ld2(aux + r0, av[0], av[1]); if (z0) sell_ld2(dinv + r0, dv[0], dv[1]); }
+    if (!TINV && (MODE == 3 || MODE == 4)) sell_ld2(dinv + r0, dv[0], dv[1]);
+    if (MODE == 5 || MODE == 6) { sell_ld2(y + r0, tv[0], tv[1]); sell_ld2(aux + r0, av[0], av[1]); if (!TINV && z0) sell_ld2(dinv + r0, dv[0], dv[1]); }
     return;
   }
 #pragma unroll
@@ -43,8 +44,8 @@ __device__ __forceinline__ void sell_prologue(const double* __restrict__ x, cons
     if (act[i]) {
       if (MODE == 1 || (MODE >= 3 && MODE <= 5) || MODE == 7) bv[i] = b[r0 + i];
       if ((MODE >= 2 && MODE <= 4) || MODE == 7) xr[i] = x[r0 + i];
-      if (MODE == 3 || MODE == 4) dv[i] = dinv[r0 + i];
-      if (MODE == 5 || MODE == 6) { tv[i] = y[r0 + i]; av[i] = aux[r0 + i]; if (z0) dv[i] = dinv[r0 + i]; }
+      if (!TINV && (MODE == 3 || MODE == 4)) dv[i] = dinv[r0 + i];
+      if (MODE == 5 || MODE == 6) { tv[i] = y[r0 + i]; av[i] = aux[r0 + i]; if (!TINV && z0) dv[i] = dinv[r0 + i]; }
     }
   }
 }
@@ -116,26 +117,44 @@ __device__ __forceinline__ void sell_epilogue(const double (&acc)[RPT], const do
 // of `group` consecutive chunks (group 1 = plain grid-stride order); workgroups with equal blockIdx % 8 share an XCD.
 // DICT: the coefficients come from the row dictionary (struct SellDict): dtab = its table in LDS, cls = the classes;
 // x loads, order of the sums and epilogue are the plain kernel's, so the products are bit-identical
-template <int KIND, int MODE, int RPT, bool CLAMP, bool SYM = false, bool DICT = false>
+// TINV (with DICT, modes 3 - 6): the epilogue's 1 / a_ii is dinvt[class] (SellDict::inv in LDS) - the class of the row in this
+// operator's dictionary (modes 3 / 4: dinv is its own diagonal's) or in the dictionary cls_d of the operator whose diagonal it is
+// (modes 5 / 6); the per-assembly check makes every row's entries those of its class bit for bit, and the table holds the
+// assembly's expression of the class's diagonal: the same double the dinv array holds for the row
+template <int KIND, int MODE, int RPT, bool CLAMP, bool SYM = false, bool DICT = false, bool TINV = false>
 __device__ __forceinline__ void sell_rows(const double* __restrict__ val, int64_t ld, const double* __restrict__ x,
                                           const double* __restrict__ b, const double* __restrict__ dinv, double w,
                                           double* __restrict__ y, double* __restrict__ aux, double* __restrict__ z0,
                                           int64_t n, int px, int64_t pxy, int64_t r0, double& dotacc, int64_t dlo,
                                           int64_t dhi, double* dotx = nullptr, int flags = 0,
-                                          const uint16_t* __restrict__ cls = nullptr, const double* dtab = nullptr) {
+                                          const uint16_t* __restrict__ cls = nullptr, const double* dtab = nullptr,
+                                          const uint16_t* __restrict__ cls_d = nullptr, const double* dinvt = nullptr) {
   using ST = SellSt<KIND>;
   double acc[RPT];
   double bv[RPT], xr[RPT], dv[RPT], tv[RPT], av[RPT];
   bool act[RPT];
-  sell_prologue<MODE, RPT, CLAMP>(x, b, dinv, y, aux, z0, n, r0, acc, bv, xr, dv, tv, av, act);
+  sell_prologue<MODE, RPT, CLAMP, DICT && TINV>(x, b, dinv, y, aux, z0, n, r0, acc, bv, xr, dv, tv, av, act);
   int cb[RPT];   // DICT: offset of the row's class in the table
   if constexpr (DICT) {
+    int cd[RPT];   // TINV: the class that determines the row's 1 / a_ii
     if constexpr (RPT == 2 && !CLAMP) {
       const uint32_t two = *reinterpret_cast<const uint32_t*>(cls + r0);   // (r0 even, cls 256-byte aligned)
       cb[0] = (int)(two & 0xffffu) * ST::S; cb[1] = (int)(two >> 16) * ST::S;
+      if constexpr (TINV) {
+        const uint32_t twod = (MODE >= 5) ? *reinterpret_cast<const uint32_t*>(cls_d + r0) : two;
+        cd[0] = (int)(twod & 0xffffu); cd[1] = (int)(twod >> 16);
+      }
     } else {
 #pragma unroll
-      for (int i = 0; i < RPT; ++i) cb[i] = act[i] ? (int)cls[r0 + i] * ST::S : 0;
+      for (int i = 0; i < RPT; ++i) {
+        const int c = act[i] ? (int)cls[r0 + i] : 0;
+        cb[i] = c * ST::S;
+        if constexpr (TINV) cd[i] = (MODE >= 5) ? (act[i] ? (int)cls_d[r0 + i] : 0) : c;
+      }
+    }
+    if constexpr (TINV) {
+#pragma unroll
+      for (int i = 0; i < RPT; ++i) dv[i] = act[i] ? dinvt[cd[i]] : 0.0;
     }
   }
   int slot = 0;
@@ -226,9 +245,21 @@ __device__ __forceinline__ void sell_rows(const double* __restrict__ val, int64_
   sell_epilogue<MODE, RPT>(acc, bv, xr, dv, tv, av, act, w, y, aux, z0, r0, dotacc, dlo, dhi, dotx, flags);
 }
 
-struct SellDictArgs { const uint16_t* cls; const double* tab; const int* state; int ncls; int zconst; };   // zconst: SellDict::zconst
+struct SellDictArgs {
+  const uint16_t* cls; const double* tab; const int* state; int ncls; int zconst;   // zconst: SellDict::zconst
+  // TINV kernels: the table of inverse diagonals (SellDict::inv) and its length; modes 5 / 6: of the dictionary of the operator
+  // whose diagonal the epilogue divides by, with that dictionary's class array and status words (modes 3 / 4: null, the own)
+  const double* inv; int ninv; const uint16_t* cls_d; const int* state_d;
+};
+// dok of a TINV launch in modes 5 / 6: both dictionaries must be this assembly's (a refused second one sends the launch down
+// the stored-value path like a refused first one: the host retires either at the end of the solve, sell_dict_poll)
+__device__ __forceinline__ bool sell_dict_ok(const SellDictArgs& da, bool second) {
+  bool ok = da.state[0] == da.ncls && da.state[1] == 1;
+  if (second) ok = ok && da.state_d[0] == da.ninv && da.state_d[1] == 1;
+  return ok;
+}
 
-template <int KIND, int MODE, int RPT, bool SYM = false, bool DICT = false>
+template <int KIND, int MODE, int RPT, bool SYM = false, bool DICT = false, bool TINV = false>
 __global__ __launch_bounds__(256) void k_spmv_sell(const double* __restrict__ val, int64_t ld,
                                                    const double* __restrict__ x, const double* __restrict__ b,
                                                    const double* __restrict__ dinv, const double* __restrict__ wp,
@@ -242,10 +273,15 @@ __global__ __launch_bounds__(256) void k_spmv_sell(const double* __restrict__ va
   // host sized the launch for; otherwise (check failed, rebuilt with another class count) the plain path below
   extern __shared__ double dtab[];
   bool dok = false;
+  const double* dinvt = nullptr;   // TINV: the inverse diagonals of the classes, behind the table
   if constexpr (DICT) {
-    dok = da.state[0] == da.ncls && da.state[1] == 1;
+    dok = sell_dict_ok(da, TINV && MODE >= 5);
     if (dok) {
       for (int i = threadIdx.x; i < da.ncls * SellSt<KIND>::S; i += 256) dtab[i] = da.tab[i];
+      if constexpr (TINV) {
+        for (int i = threadIdx.x; i < da.ninv; i += 256) dtab[da.ncls * SellSt<KIND>::S + i] = da.inv[i];
+        dinvt = dtab + da.ncls * SellSt<KIND>::S;
+      }
       __syncthreads();
     }
   }
@@ -300,9 +336,9 @@ __global__ __launch_bounds__(256) void k_spmv_sell(const double* __restrict__ va
     if constexpr (DICT) {
       if (dok) {
         if (c0 >= halo && c0 + CH + halo <= n)
-          sell_rows<KIND, MODE, RPT, false, SYM, true>(val, ld, x, b, dinv, w, y, aux, z0, n, px, pxy, r0, dotacc, dlo, dhi, dotx, flags, da.cls, dtab);
+          sell_rows<KIND, MODE, RPT, false, SYM, true, TINV>(val, ld, x, b, dinv, w, y, aux, z0, n, px, pxy, r0, dotacc, dlo, dhi, dotx, flags, da.cls, dtab, da.cls_d, dinvt);
         else
-          sell_rows<KIND, MODE, RPT, true, SYM, true>(val, ld, x, b, dinv, w, y, aux, z0, n, px, pxy, r0, dotacc, dlo, dhi, dotx, flags, da.cls, dtab);
+          sell_rows<KIND, MODE, RPT, true, SYM, true, TINV>(val, ld, x, b, dinv, w, y, aux, z0, n, px, pxy, r0, dotacc, dlo, dhi, dotx, flags, da.cls, dtab, da.cls_d, dinvt);
         continue;
       }
     }
@@ -353,46 +389,57 @@ __device__ __forceinline__ void dictw_load_plane(const double* __restrict__ x, i
 }
 
 // operands of one step besides the x window: classes and the epilogue's vectors, requested one step ahead
-struct DwOps { double bv[2], dv[2], tv[2], av[2]; uint32_t cls2; };   // cls2: the two classes as loaded (low / high half)
+struct DwOps { double bv[2], dv[2], tv[2], av[2]; uint32_t cls2, clsd; };   // cls2: the two classes as loaded (low / high half); clsd: TINV, modes 5 / 6 - those of the second dictionary
 
 // ALL: both rows of every lane are inside the plane (all position chunks but the last of a plane) - no lane masks, no
 // branches: the 4-step loop must stay straight-line code, or the compiler's wait-count pass drains every outstanding
 // request at each join and the requests of the next step are never in flight while this one computes
 // NOCLS: the classes of the pair are those of the plane below (SellDict::zconst), the caller copies them
-template <int MODE, bool ALL, bool NOCLS = false>
+// TINV: no dinv load - the step takes 1 / a_ii from the table of inverse diagonals by class (dictw_step); in modes 5 / 6 by the
+// class in the second dictionary, cls_d, loaded (or copied) exactly as the first
+template <int MODE, bool ALL, bool NOCLS = false, bool TINV = false>
 __device__ __forceinline__ void dictw_fetch(DwOps& o, const uint16_t* __restrict__ cls, const double* __restrict__ b,
                                             const double* __restrict__ dinv, const double* __restrict__ y,
                                             const double* __restrict__ aux, const double* __restrict__ z0, int64_t r0, bool a0,
-                                            bool a1) {
+                                            bool a1, const uint16_t* __restrict__ cls_d = nullptr) {
   const bool act[2] = {a0, a1};
+  constexpr bool SECOND = TINV && MODE >= 5;
   if (ALL || (a0 && a1)) {
     o.bv[0] = o.bv[1] = 0.0; o.dv[0] = o.dv[1] = 0.0; o.tv[0] = o.tv[1] = 0.0; o.av[0] = o.av[1] = 0.0;
     if (!NOCLS) o.cls2 = (uint32_t)cls[r0] | ((uint32_t)cls[r0 + 1] << 16);   // (two aligned 2-byte loads: r0 is odd on every other plane)
+    if (!NOCLS && SECOND) o.clsd = (uint32_t)cls_d[r0] | ((uint32_t)cls_d[r0 + 1] << 16);
     if (MODE == 1 || (MODE >= 3 && MODE <= 5) || MODE == 7) sell_ld2(b + r0, o.bv[0], o.bv[1]);
-    if (MODE == 3 || MODE == 4) sell_ld2(dinv + r0, o.dv[0], o.dv[1]);
-    if (MODE == 5 || MODE == 6) { sell_ld2(y + r0, o.tv[0], o.tv[1]); sell_ld2(aux + r0, o.av[0], o.av[1]); if (z0) sell_ld2(dinv + r0, o.dv[0], o.dv[1]); }
+    if (!TINV && (MODE == 3 || MODE == 4)) sell_ld2(dinv + r0, o.dv[0], o.dv[1]);
+    if (MODE == 5 || MODE == 6) { sell_ld2(y + r0, o.tv[0], o.tv[1]); sell_ld2(aux + r0, o.av[0], o.av[1]); if (!TINV && z0) sell_ld2(dinv + r0, o.dv[0], o.dv[1]); }
     return;
   }
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    if (i == 0) o.cls2 = 0;
+    if (i == 0) { o.cls2 = 0; if (SECOND) o.clsd = 0; }
     o.bv[i] = 0.0; o.dv[i] = 0.0; o.tv[i] = 0.0; o.av[i] = 0.0;
     if (act[i]) {
       o.cls2 |= (uint32_t)cls[r0 + i] << (16 * i);
+      if (SECOND) o.clsd |= (uint32_t)cls_d[r0 + i] << (16 * i);
       if (MODE == 1 || (MODE >= 3 && MODE <= 5) || MODE == 7) o.bv[i] = b[r0 + i];
-      if (MODE == 3 || MODE == 4) o.dv[i] = dinv[r0 + i];
-      if (MODE == 5 || MODE == 6) { o.tv[i] = y[r0 + i]; o.av[i] = aux[r0 + i]; if (z0) o.dv[i] = dinv[r0 + i]; }
+      if (!TINV && (MODE == 3 || MODE == 4)) o.dv[i] = dinv[r0 + i];
+      if (MODE == 5 || MODE == 6) { o.tv[i] = y[r0 + i]; o.av[i] = aux[r0 + i]; if (!TINV && z0) o.dv[i] = dinv[r0 + i]; }
     }
   }
 }
 
-template <int MODE, bool ALL>
+template <int MODE, bool ALL, bool TINV = false>
 __device__ __forceinline__ void dictw_step(const double (&lo)[3][4], const double (&mid)[3][4], const double (&hi)[3][4],
                                            const DwOps& o, const double* dtab, double w, double* __restrict__ y, double* __restrict__ aux,
                                            double* __restrict__ z0, int64_t r0, bool a0, bool a1, double& dotacc, int64_t dlo,
-                                           int64_t dhi, double* dotx, int flags) {
+                                           int64_t dhi, double* dotx, int flags, const double* dinvt = nullptr) {
   double acc[2] = {0.0, 0.0}, xr[2] = {0.0, 0.0};
   const bool act[2] = {ALL || a0, ALL || a1};
+  double dvt[2] = {0.0, 0.0};
+  if constexpr (TINV) {   // two LDS reads by class instead of the 16-byte dinv load (a row that is not active reads class 0 and is not stored)
+    const uint32_t c = (MODE >= 5) ? o.clsd : o.cls2;
+    dvt[0] = dinvt[c & 0xffffu]; dvt[1] = dinvt[c >> 16];
+  }
+  const double (&dv)[2] = TINV ? dvt : o.dv;
   if ((MODE >= 2 && MODE <= 4) || MODE == 7) {   // x[r0 + i]
     xr[0] = act[0] ? mid[1][1] : 0.0;
     xr[1] = act[1] ? mid[1][2] : 0.0;
@@ -424,7 +471,7 @@ __device__ __forceinline__ void dictw_step(const double (&lo)[3][4], const doubl
     for (int i = 0; i < 2; ++i) acc[i] = (pa[0][i] + pa[1][i]) + pa[2][i];
 #endif
   }
-  sell_epilogue<MODE, 2>(acc, o.bv, xr, o.dv, o.tv, o.av, act, w, y, aux, z0, r0, dotacc, dlo, dhi, dotx, 0);   // (no store-hint experiments here: a branch around the stores costs the pipelining)
+  sell_epilogue<MODE, 2>(acc, o.bv, xr, dv, o.tv, o.av, act, w, y, aux, z0, r0, dotacc, dlo, dhi, dotx, 0);   // (no store-hint experiments here: a branch around the stores costs the pipelining)
 }
 
 #ifdef PPH_DW_STAMPS
@@ -434,7 +481,9 @@ __device__ unsigned long long* g_dw_stamps = nullptr;
 #else
 #define PPH_DW_STAMP(I) do { } while (0)
 #endif
-template <int MODE, bool ZC>
+// TINV (modes 3 - 6): the epilogue's 1 / a_ii comes from the table of inverse diagonals behind dtab in LDS, by the row's class
+// (modes 5 / 6: by its class in the second dictionary, da.cls_d) - no dinv stream (sell_rows; the launcher decides: sell_dinv_table)
+template <int MODE, bool ZC, bool TINV = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE <= 1 ? 3 : 2, 4))) void k_spmv_dict_walk(const double* __restrict__ val, int64_t ld,
                                                         const double* __restrict__ x, const double* __restrict__ b,
                                                         const double* __restrict__ dinv, const double* __restrict__ wp,
@@ -448,9 +497,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE <= 1 ?
   int sti = 3;
   PPH_DW_STAMP(0);
 #endif
-  const bool dok = da.state[0] == da.ncls && da.state[1] == 1;
+  const bool dok = sell_dict_ok(da, TINV && MODE >= 5);
+  const double* const dinvt = dtab + da.ncls * 27;
   if (dok) {
     for (int i = threadIdx.x; i < da.ncls * 27; i += 256) dtab[i] = da.tab[i];
+    if constexpr (TINV)
+      for (int i = threadIdx.x; i < da.ninv; i += 256) dtab[da.ncls * 27 + i] = da.inv[i];
     __syncthreads();
   }
   PPH_DW_STAMP(1);
@@ -491,12 +543,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE <= 1 ?
       else dictw_load_plane<true>(x, (int64_t)zz_ * pxy + p, px, n, W);                                           \
     } while (0)
 #define PPH_DW_LOAD(W, ZZ) dictw_load_plane<false>(x, (int64_t)(ZZ) * pxy + p, px, n, W)
-#define PPH_DW_FETCH(O, ZZ) dictw_fetch<MODE, false>(O, da.cls, b, dinv, y, aux, z0, (int64_t)(ZZ) * pxy + p, a0, a1)
+#define PPH_DW_FETCH(O, ZZ) dictw_fetch<MODE, false, false, TINV>(O, da.cls, b, dinv, y, aux, z0, (int64_t)(ZZ) * pxy + p, a0, a1, da.cls_d)
 #define PPH_DW_STEP(LO, MID, HI, O, ZZ)                                                                         \
-    dictw_step<MODE, false>(LO, MID, HI, O, dtab, w, y, aux, z0, (int64_t)(ZZ) * pxy + p, a0, a1, dotacc, dlo, dhi, dotx, flags)
-#define PPH_DW_FETCHA(O, ZZ) dictw_fetch<MODE, true>(O, da.cls, b, dinv, y, aux, z0, (int64_t)(ZZ) * pxy + p, true, true)
+    dictw_step<MODE, false, TINV>(LO, MID, HI, O, dtab, w, y, aux, z0, (int64_t)(ZZ) * pxy + p, a0, a1, dotacc, dlo, dhi, dotx, flags, dinvt)
+#define PPH_DW_FETCHA(O, ZZ) dictw_fetch<MODE, true, false, TINV>(O, da.cls, b, dinv, y, aux, z0, (int64_t)(ZZ) * pxy + p, true, true, da.cls_d)
 #define PPH_DW_STEPA(LO, MID, HI, O, ZZ)                                                                        \
-    dictw_step<MODE, true>(LO, MID, HI, O, dtab, w, y, aux, z0, (int64_t)(ZZ) * pxy + p, true, true, dotacc, dlo, dhi, dotx, flags)
+    dictw_step<MODE, true, TINV>(LO, MID, HI, O, dtab, w, y, aux, z0, (int64_t)(ZZ) * pxy + p, true, true, dotacc, dlo, dhi, dotx, flags, dinvt)
     PPH_DW_LOADC(A, z - 1);
     PPH_DW_LOADC(B, z);
     PPH_DW_LOADC(C, z + 1);
@@ -525,10 +577,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE <= 1 ?
         // that range a step takes its classes from the step below: no class load, one word less in flight.
 #define PPH_DW_FETCHN(O, OP, ZZ)                                                                                  \
         do {                                                                                                      \
-          dictw_fetch<MODE, true, true>(O, da.cls, b, dinv, y, aux, z0, (int64_t)(ZZ) * pxy + p, true, true);     \
+          dictw_fetch<MODE, true, true, TINV>(O, da.cls, b, dinv, y, aux, z0, (int64_t)(ZZ) * pxy + p, true, true); \
           uint32_t c_ = (OP).cls2;                                                                                \
           asm volatile("" : "+v"(c_));   /* (opaque: or the 54 table reads are hoisted out of the loop - 108 registers) */ \
           (O).cls2 = c_;                                                                                          \
+          if (TINV && MODE >= 5) (O).clsd = (OP).clsd;   /* (the second dictionary's classes are constant along z here as well: sell_dinv_table) */ \
         } while (0)
         while (z + 4 <= zend && z + 4 <= planes - 3) {
           PPH_DW_LOAD(D, z + 2); PPH_DW_FETCHN(O1, O0, z + 1); PPH_DW_STEPA(A, B, C, O0, z);
@@ -601,15 +654,43 @@ int sell_dw_stamps(pph_ctx* ctx, int on) {
 }
 #endif
 
+// whole-operator products on a usable dictionary the walk kernel takes
+static bool sell_walk_applies(const pph_ctx* ctx, const Sell& E, int64_t n) {
+  const int64_t pxy = (int64_t)E.px * E.py;
+  return ctx->sell_dict_walk && E.kind == PPH_CELL_HEX && E.pz >= 4 && pxy >= 2048 && n == pxy * E.pz;
+}
+
+bool sell_dinv_table(const pph_ctx* ctx, const Sell& E, int64_t n, int mode, bool has_z0, const SellDict* dd) {
+  if (!ctx->sell_dict_dinv || !dd || !dd->on || !dd->inv.p) return false;
+  if (ctx->sell_rpt == 1 || !E.sym || !E.dict || !E.dict->on) return false;   // (no dictionary product: sell_spmv)
+  if (mode == 3 || mode == 4) return dd == E.dict;
+  if ((mode != 5 && mode != 6) || !has_z0) return false;
+  if (dd->n != n || dd->px != E.px || dd->py != E.py) return false;
+  // the kernel that copies the product's classes from the plane below copies the second dictionary's too
+  const bool zc = sell_walk_applies(ctx, E, n) && E.dict->zconst && ctx->sell_dict_zconst && E.pz >= 8;
+  return !zc || dd->zconst;
+}
+
+// kernel arguments of a dictionary product; dd != null: with the table of inverse diagonals the mode reads
+static SellDictArgs sell_dict_args(const SellDict& D, int zconst, int mode, const SellDict* dd) {
+  SellDictArgs da = {D.cls.p, D.tab.p, D.state.p, D.ncls, zconst, nullptr, 0, nullptr, nullptr};
+  if (dd) {
+    da.inv = dd->inv.p; da.ninv = dd->ncls;
+    if (mode >= 5) { da.cls_d = dd->cls.p; da.state_d = dd->state.p; }
+  }
+  return da;
+}
+
 // launches the walk kernel for a whole-operator product on a usable dictionary; returns the grid, 0 = not applicable
 static int sell_launch_dict_walk(pph_ctx* ctx, int mode, const Sell& E, const double* x, const double* b, const double* dinv,
                                  const double* w, double* y, double* aux, double* z0, int64_t n, double* part, int64_t dlo,
-                                 int64_t dhi) {
+                                 int64_t dhi, const SellDict* dd) {
   const int64_t pxy = (int64_t)E.px * E.py;
-  if (!ctx->sell_dict_walk || E.kind != PPH_CELL_HEX || E.pz < 4 || pxy < 2048 || n != pxy * E.pz) return 0;
+  if (!sell_walk_applies(ctx, E, n)) return 0;
   const SellDict& D = *E.dict;
-  const SellDictArgs da = {D.cls.p, D.tab.p, D.state.p, D.ncls, (D.zconst && ctx->sell_dict_zconst && E.pz >= 8) ? 1 : 0};
-  const size_t lds = (size_t)D.ncls * 27 * sizeof(double);
+  const SellDictArgs da = sell_dict_args(D, (D.zconst && ctx->sell_dict_zconst && E.pz >= 8) ? 1 : 0, mode, dd);
+  const bool tinv = dd != nullptr;   // (sell_spmv passes it only where sell_dinv_table says so)
+  const size_t lds = ((size_t)D.ncls * 27 + (size_t)da.ninv) * sizeof(double);
   const int64_t items = ((pxy + 511) / 512) * E.pz;
   int64_t g = ctx->sell_dict_blocks >= 8 ? ctx->sell_dict_blocks : 1024;
   if ((mode == 2 || mode >= 4) && g > ctx->part_cap) g = ctx->part_cap;
@@ -626,16 +707,27 @@ static int sell_launch_dict_walk(pph_ctx* ctx, int mode, const Sell& E, const do
       hipLaunchKernelGGL((k_spmv_dict_walk<MM, false>), dim3(grid), dim3(256), lds, ctx->stream, E.val, E.ld, x, b, dinv, w, y, aux, \
                          z0, n, E.px, pxy, E.pz, part, dlo, dhi, ctx->sell_flags, da);                                       \
   } while (0)
+#define PPH_DW_GOT(MM)                                                                                                      \
+  do {                                                                                                                       \
+    if (!tinv) { PPH_DW_GO(MM); break; }                                                                                     \
+    if (da.zconst)                                                                                                           \
+      hipLaunchKernelGGL((k_spmv_dict_walk<MM, true, true>), dim3(grid), dim3(256), lds, ctx->stream, E.val, E.ld, x, b, dinv, w, y, \
+                         aux, z0, n, E.px, pxy, E.pz, part, dlo, dhi, ctx->sell_flags, da);                                  \
+    else                                                                                                                     \
+      hipLaunchKernelGGL((k_spmv_dict_walk<MM, false, true>), dim3(grid), dim3(256), lds, ctx->stream, E.val, E.ld, x, b, dinv, w, y, \
+                         aux, z0, n, E.px, pxy, E.pz, part, dlo, dhi, ctx->sell_flags, da);                                  \
+  } while (0)
   switch (mode) {
     case 0: PPH_DW_GO(0); break;
     case 1: PPH_DW_GO(1); break;
     case 2: PPH_DW_GO(2); break;
-    case 3: PPH_DW_GO(3); break;
-    case 4: PPH_DW_GO(4); break;
-    case 5: PPH_DW_GO(5); break;
-    case 6: PPH_DW_GO(6); break;
+    case 3: PPH_DW_GOT(3); break;
+    case 4: PPH_DW_GOT(4); break;
+    case 5: PPH_DW_GOT(5); break;
+    case 6: PPH_DW_GOT(6); break;
     default: PPH_DW_GO(7); break;
   }
+#undef PPH_DW_GOT
 #undef PPH_DW_GO
   return grid;
 }
@@ -644,11 +736,11 @@ static int sell_launch_dict_walk(pph_ctx* ctx, int mode, const Sell& E, const do
 template <int KIND, int RPT>
 static void sell_launch_mode(pph_ctx* ctx, int mode, int grid, const Sell& E, const double* x, const double* b,
                              const double* dinv, const double* w, double* y, double* aux, double* z0, int64_t n, int64_t nchunks, int64_t chunk0,
-                             int group, double* part, int64_t dlo, int64_t dhi) {
+                             int group, double* part, int64_t dlo, int64_t dhi, const SellDict* dd) {
   const int64_t pxy = (int64_t)E.px * E.py;
   const int64_t halo = (E.pz > 1 ? pxy : 0) + E.px + 2;   // reach of the x window of a row (2D: no z lines)
   int zwalk = (E.sym && E.pz > 2 && ctx->sell_zwalk > 0 && chunk0 == 0 && nchunks >= ctx->sell_zwalk_min_chunks) ? ctx->sell_zwalk : 0;   // (no gain on full storage)
-  const SellDictArgs nod = {nullptr, nullptr, nullptr, 0, 0};
+  const SellDictArgs nod = {nullptr, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, nullptr};
 #define PPH_SELL_GO(MM)                                                                                              \
   hipLaunchKernelGGL((k_spmv_sell<KIND, MM, RPT>), dim3(grid), dim3(256), 0, ctx->stream, E.val, E.ld, x, b, dinv, w, \
                      y, aux, z0, n, E.px, pxy, halo, nchunks, chunk0, group, zwalk, ctx->sell_xmap, part, dlo, dhi, ctx->sell_flags, nod)
@@ -656,9 +748,23 @@ static void sell_launch_mode(pph_ctx* ctx, int mode, int grid, const Sell& E, co
     if (E.sym && E.dict && E.dict->on) {
       // row dictionary: 2 B per row instead of the value streams; the table of distinct rows goes to LDS
       const SellDict& D = *E.dict;
-      const SellDictArgs da = {D.cls.p, D.tab.p, D.state.p, D.ncls, 0};
-      const size_t lds = (size_t)D.ncls * SellSt<KIND>::S * sizeof(double);
+      const SellDictArgs da = sell_dict_args(D, 0, mode, dd);
+      const size_t lds = ((size_t)D.ncls * SellSt<KIND>::S + (size_t)da.ninv) * sizeof(double);
       if (ctx->sell_dict_zwalk >= 0) zwalk = (E.pz > 2 && chunk0 == 0) ? ctx->sell_dict_zwalk : 0;
+      if (dd) {   // 1 / a_ii from the table of inverse diagonals (sell_dinv_table)
+#define PPH_SELL_GODT(MM)                                                                                                      \
+  hipLaunchKernelGGL((k_spmv_sell<KIND, MM, 2, true, true, true>), dim3(grid), dim3(256), lds, ctx->stream, E.val, E.ld, x, b, \
+                     dinv, w, y, aux, z0, n, E.px, pxy, halo, nchunks, chunk0, group, zwalk, ctx->sell_xmap, part, dlo, dhi,   \
+                     ctx->sell_flags, da)
+        switch (mode) {
+          case 3: PPH_SELL_GODT(3); break;
+          case 4: PPH_SELL_GODT(4); break;
+          case 5: PPH_SELL_GODT(5); break;
+          default: PPH_SELL_GODT(6); break;
+        }
+#undef PPH_SELL_GODT
+        return;
+      }
 #define PPH_SELL_GOD(MM)                                                                                                       \
   hipLaunchKernelGGL((k_spmv_sell<KIND, MM, 2, true, true>), dim3(grid), dim3(256), lds, ctx->stream, E.val, E.ld, x, b, dinv, \
                      w, y, aux, z0, n, E.px, pxy, halo, nchunks, chunk0, group, zwalk, ctx->sell_xmap, part, dlo, dhi,         \
@@ -710,7 +816,7 @@ static void sell_launch_mode(pph_ctx* ctx, int mode, int grid, const Sell& E, co
 // launches the product; returns the grid (= number of partial sums written in mode 2)
 int sell_spmv(pph_ctx* ctx, const Sell& E, int64_t n, int mode, const double* x, const double* b, const double* dinv,
               const double* w, double* y, double* part, int64_t dlo, int64_t dhi, double* aux, double* z0, int64_t cbeg, int64_t cend,
-              int grid_cap) {
+              int grid_cap, const SellDict* dinv_dict) {
   const int rpt = (ctx->sell_rpt == 1) ? 1 : 2;
   // [cbeg, cend) (cend < 0: all): the chunks of this launch - a product split into boundary and interior rows
   const int64_t nchunks_all = ceil_div64(n, 256 * rpt);
@@ -726,8 +832,11 @@ int sell_spmv(pph_ctx* ctx, const Sell& E, int64_t n, int mode, const double* x,
   // (a plain product reads the stored values: whole before it runs, ValuesState; status ignored here as for the launches below -
   // a failed launch surfaces at the caller's next check of the stream)
   if (!dict) (void)sell_values_ensure_for(ctx, E.val);
+  // the dictionary whose table of inverse diagonals replaces the dinv stream of this launch (null: the stream is read)
+  const SellDict* dd = (cend < 0 && sell_dinv_table(ctx, E, n, mode, z0 != nullptr, dinv_dict)) ? dinv_dict : nullptr;
+  if (dd) ctx->n_dict_dinv++;
   if (dict && cend < 0) {
-    const int g = sell_launch_dict_walk(ctx, mode, E, x, b, dinv, w, y, aux, z0, n, part, dlo, dhi);
+    const int g = sell_launch_dict_walk(ctx, mode, E, x, b, dinv, w, y, aux, z0, n, part, dlo, dhi, dd);
     if (g > 0) return g;
   }
   int cap = (ctx->sell_blocks >= 8 && ctx->sell_blocks <= 8192) ? (ctx->sell_blocks / 8) * 8
@@ -742,8 +851,8 @@ int sell_spmv(pph_ctx* ctx, const Sell& E, int64_t n, int mode, const double* x,
   const int grid = (int)g;
   int group = ctx->sell_group > 0 ? ctx->sell_group : 1;
 #define PPH_SELL_KIND(KK)                                                                                     \
-  if (rpt == 1) sell_launch_mode<KK, 1>(ctx, mode, grid, E, x, b, dinv, w, y, aux, z0, n, nchunks, chunk0, group, part, dlo, dhi); \
-  else sell_launch_mode<KK, 2>(ctx, mode, grid, E, x, b, dinv, w, y, aux, z0, n, nchunks, chunk0, group, part, dlo, dhi)
+  if (rpt == 1) sell_launch_mode<KK, 1>(ctx, mode, grid, E, x, b, dinv, w, y, aux, z0, n, nchunks, chunk0, group, part, dlo, dhi, nullptr); \
+  else sell_launch_mode<KK, 2>(ctx, mode, grid, E, x, b, dinv, w, y, aux, z0, n, nchunks, chunk0, group, part, dlo, dhi, dd)
   switch (E.kind) {
     case PPH_CELL_QUAD: PPH_SELL_KIND(PPH_CELL_QUAD); break;
     case PPH_CELL_TRI: PPH_SELL_KIND(PPH_CELL_TRI); break;
@@ -817,15 +926,19 @@ __global__ __launch_bounds__(256) void k_dict_build(const double* __restrict__ v
 
 // pass 2 (one workgroup): classes = occupied hash slots in slot order; tab[class] = the coefficients of its
 // representative row.  refresh: the classes are known from an earlier assembly, only the table is read again.
+// inv[class] = 1 / its diagonal entry (slot S / 2) in the assembly's expression (pph_assemble.hip: i1 / i2), what the dinv
+// array of the operator holds for every row of the class (SellDict::inv)
+__device__ __forceinline__ double dict_inv_diag(double t) { return (t != 0.0) ? 1.0 / t : 1.0; }
 __global__ __launch_bounds__(256) void k_dict_table(const double* __restrict__ val, int64_t ld, int sym, Stencil st, int px,
                                                     int64_t pxy, int64_t n, const unsigned long long* __restrict__ keys,
                                                     int64_t* rep, uint16_t* __restrict__ map, double* __restrict__ tab,
-                                                    int* state, int cap, int refresh, int ncls) {
+                                                    double* __restrict__ inv, int* state, int cap, int refresh, int ncls) {
   const int S = st.count;
   if (refresh) {
     for (int c = threadIdx.x; c < ncls; c += 256) {
       const int64_t row = rep[PPH_DICT_HASH + c];
       for (int s = 0; s < S; ++s) tab[c * S + s] = sell_coef(val, ld, sym, S, s, row, sell_off(st, s, px, pxy), n);
+      inv[c] = dict_inv_diag(tab[c * S + S / 2]);
     }
     if (threadIdx.x == 0) { state[0] = ncls; state[1] = 1; }
     return;
@@ -854,6 +967,7 @@ __global__ __launch_bounds__(256) void k_dict_table(const double* __restrict__ v
     map[slot] = (uint16_t)id;
     rep[PPH_DICT_HASH + id] = row;
     for (int s = 0; s < S; ++s) tab[id * S + s] = sell_coef(val, ld, sym, S, s, row, sell_off(st, s, px, pxy), n);
+    inv[id] = dict_inv_diag(tab[id * S + S / 2]);
     ++id;
   }
   if (threadIdx.x == 0) { state[0] = total; state[1] = 1; }
@@ -992,7 +1106,7 @@ int sell_dict_update(pph_ctx* ctx, Sell* E, SellDict& D, int64_t n) {
   if (same && D.on) {
     // re-assembly: same classes expected - re-read the table from the representatives, check every row
     hipLaunchKernelGGL(k_dict_table, dim3(1), dim3(256), 0, ctx->stream, E->val, E->ld, E->sym, st, E->px, pxy, n, D.keys.p,
-                       D.rep.p, D.map.p, D.tab.p, D.state.p, cap, 1, D.ncls);
+                       D.rep.p, D.map.p, D.tab.p, D.inv.p, D.state.p, cap, 1, D.ncls);
     dict_launch_verify(ctx, *E, D, n, nullptr, D.ncls);
     PPH_HIP(ctx, hipGetLastError());
     E->dict = &D;
@@ -1007,6 +1121,7 @@ int sell_dict_update(pph_ctx* ctx, Sell* E, SellDict& D, int64_t n) {
   PPH_TRY(D.rep.alloc(ctx, (size_t)(PPH_DICT_HASH + PPH_DICT_CAP)));
   PPH_TRY(D.map.alloc(ctx, (size_t)PPH_DICT_HASH));
   PPH_TRY(D.tab.alloc(ctx, (size_t)PPH_DICT_CAP * 27));
+  PPH_TRY(D.inv.alloc(ctx, (size_t)PPH_DICT_CAP));
   PPH_TRY(D.state.alloc(ctx, 4));
   PPH_HIP(ctx, hipMemsetAsync(D.cls.p, 0, (size_t)E->ld * sizeof(uint16_t), ctx->stream));
   PPH_HIP(ctx, hipMemsetAsync(D.keys.p, 0, (size_t)PPH_DICT_HASH * sizeof(unsigned long long), ctx->stream));
@@ -1014,7 +1129,7 @@ int sell_dict_update(pph_ctx* ctx, Sell* E, SellDict& D, int64_t n) {
   hipLaunchKernelGGL(k_dict_build, dim3(grid), dim3(256), 0, ctx->stream, E->val, E->ld, E->sym, st, E->px, pxy, n, D.keys.p,
                      D.rep.p, D.cls.p, D.state.p, cap);
   hipLaunchKernelGGL(k_dict_table, dim3(1), dim3(256), 0, ctx->stream, E->val, E->ld, E->sym, st, E->px, pxy, n, D.keys.p,
-                     D.rep.p, D.map.p, D.tab.p, D.state.p, cap, 0, 0);
+                     D.rep.p, D.map.p, D.tab.p, D.inv.p, D.state.p, cap, 0, 0);
   dict_launch_verify(ctx, *E, D, n, D.map.p, cap);
   if (E->kind == PPH_CELL_HEX && n == pxy * E->pz)
     hipLaunchKernelGGL(k_dict_zconst, dim3(grid), dim3(256), 0, ctx->stream, D.cls.p, pxy, E->pz, D.state.p);
@@ -1075,13 +1190,15 @@ __global__ __launch_bounds__(256) void k_dict_adj(const uint16_t* __restrict__ c
   }
 }
 
-// tab[c][s] <- mini[src[c][s]] (0 where src < 0), then fact B on the finished table.  One workgroup per dictionary.
+// tab[c][s] <- mini[src[c][s]] (0 where src < 0) and inv[c] from the new diagonal entry, then fact B on the finished table.
+// One workgroup per dictionary.
 __global__ __launch_bounds__(256) void k_dict_tables_check(const double* __restrict__ mini, const int32_t* __restrict__ src,
-                                                           double* __restrict__ tab, const uint32_t* __restrict__ adj, int S,
-                                                           int ncls, int* state, int* alarm) {
+                                                           double* __restrict__ tab, double* __restrict__ inv,
+                                                           const uint32_t* __restrict__ adj, int S, int ncls, int* state, int* alarm) {
   const int C0 = S / 2;
   for (int i = threadIdx.x; i < ncls * S; i += 256) tab[i] = src[i] >= 0 ? mini[src[i]] : 0.0;
   __syncthreads();
+  for (int c = threadIdx.x; c < ncls; c += 256) inv[c] = dict_inv_diag(tab[c * S + C0]);
   bool bad = false;
   for (int i = threadIdx.x; i < ncls * C0; i += 256) {
     const int c = i / C0, s = i % C0;
@@ -1182,7 +1299,7 @@ int dict_group_tables(pph_ctx* ctx, DictGroup& G, SellDict* const* dicts, int nd
     SellDict* D = dicts[d];
     if (!D) continue;
     hipLaunchKernelGGL(k_dict_tables_check, dim3(1), dim3(256), 0, ctx->stream, G.mini.p + (size_t)d * SS * (size_t)G.ldm, D->src.p, D->tab.p,
-                       D->adj.p, S, D->ncls, D->state.p, ctx->dict_alarm_dev);
+                       D->inv.p, D->adj.p, S, D->ncls, D->state.p, ctx->dict_alarm_dev);
     D->checked = true;
   }
   PPH_HIP(ctx, hipGetLastError());

@@ -637,11 +637,11 @@ struct BlockSolver {
   double last_res = -1.0;
   // where a caller that produces the residual a warm CG solve of block `which` starts from may leave its first
   // pre-smoothing z0 = dinv .* r * w (then: solve(..., z0_ready = true)); false: this solve has no use for it
-  bool presmooth_target(int which, double** z0, const double** d, const double** w) {
+  bool presmooth_target(int which, double** z0, const double** d, const double** w, const SellDict** dd) {
     if (cfg->inner_ksp_type != PPH_KSP_CG || cfg->inner_pc_type != PPH_PC_MG || cfg->inner_norm == 0 || !A[which].ell.val) return false;
     const int ns = cfg->mg_smooth > 0 ? cfg->mg_smooth : 2;
     bool lo = false;
-    if (!mg_pre_smoother(ctx, which, ns, d, w, &lo)) return false;
+    if (!mg_pre_smoother(ctx, which, ns, d, w, &lo, dd)) return false;
     return work(ctx, W_IP, (size_t)ctx->n, z0) == PPH_OK;
   }
   int solve(int which, const double* rhs, double* z, bool warm, const double* r_init = nullptr, double* r_io = nullptr,
@@ -864,19 +864,20 @@ int pph_solve_device(pph_ctx* ctx, const pph_solver_cfg* cfg, pph_solve_info* in
     // the coupling products also write the first pre-smoothing of the block solve that follows them (fused cycle)
     double* z0p[2] = {nullptr, nullptr};
     const double *z0d[2] = {nullptr, nullptr}, *z0w[2] = {nullptr, nullptr};
+    const SellDict* z0c[2] = {nullptr, nullptr};   // the dictionaries of A11 / A22 while usable: z0d are their 1 / a_ii
     bool z0r[2] = {false, false};   // block 0: written by the previous sweep's last product
     if (recur && A12.ell.val && A21.ell.val)
       for (int f = 0; f < 2; ++f)
-        if (!bs.presmooth_target(f, &z0p[f], &z0d[f], &z0w[f])) z0p[f] = nullptr;
+        if (!bs.presmooth_target(f, &z0p[f], &z0d[f], &z0w[f], &z0c[f])) z0p[f] = nullptr;
     while (res > tol && its < cfg->picard_max_it) {
       const bool warm = its > 0;
       if (warm && launch_only) {
         auto sweep = [&]() -> int {
           // (the block solves start from the residuals R0 / R1: their right-hand sides are not read)
           PPH_TRY(bs.solve(0, pb, du1, true, R0, R0, -1.0, z0r[0]));
-          la_spmv_shift(ctx, A21, du1, b2, R1, rhs1, tn, S_B, pob, pob + pon, z0p[1], z0d[1], z0w[1]);   // rhs1 = b2 - A21 du1 ; R1 follows
+          la_spmv_shift(ctx, A21, du1, b2, R1, rhs1, tn, S_B, pob, pob + pon, z0p[1], z0d[1], z0w[1], z0c[1]);   // rhs1 = b2 - A21 du1 ; R1 follows
           PPH_TRY(bs.solve(1, rhs1, du2, true, R1, R1, -1.0, z0p[1] != nullptr));
-          la_spmv_shift(ctx, A12, du2, nullptr, R0, t12, tn, S_A, pob, pob + pon, z0p[0], z0d[0], z0w[0]);    // t12 = A12 du2 ; R0 follows ; ||R0||^2
+          la_spmv_shift(ctx, A12, du2, nullptr, R0, t12, tn, S_A, pob, pob + pon, z0p[0], z0d[0], z0w[0], z0c[0]);    // t12 = A12 du2 ; R0 follows ; ||R0||^2
           z0r[0] = z0p[0] != nullptr;
           la_dot(ctx, R1 + pob, R1 + pob, pon, S_A + 1);
           la_publish(ctx, S_A, 4);   // ||R0||^2, ||R1||^2, (S_B), breakdowns counted by the block solves (S_BAD)
@@ -919,7 +920,7 @@ int pph_solve_device(pph_ctx* ctx, const pph_solver_cfg* cfg, pph_solve_info* in
       double rn1 = -1.0;
       if (warm && recur) {
         // new rhs of the micro block, R1 += rhs1_new - rhs1_old, ||R1||^2 - one pass
-        la_spmv_shift(ctx, A21, du1, b2, R1, rhs1, tn, S_B, pob, pob + pon, z0p[1], z0d[1], z0w[1]);
+        la_spmv_shift(ctx, A21, du1, b2, R1, rhs1, tn, S_B, pob, pob + pon, z0p[1], z0d[1], z0w[1], z0c[1]);
         if (hints) {
           PPH_TRY(la_fetch(ctx, S_B, 1));
           rn1 = std::sqrt(ctx->h_scal[S_B]);
@@ -932,7 +933,7 @@ int pph_solve_device(pph_ctx* ctx, const pph_solver_cfg* cfg, pph_solve_info* in
       ++its;
       if (recur) {
         // new coupling term, R0 += A12 du2_old - A12 du2_new, ||R0||^2 - one pass (the first sweep: t12 = 0)
-        la_spmv_shift(ctx, A12, du2, nullptr, R0, t12, tn, S_A, pob, pob + pon, z0p[0], z0d[0], z0w[0]);
+        la_spmv_shift(ctx, A12, du2, nullptr, R0, t12, tn, S_A, pob, pob + pon, z0p[0], z0d[0], z0w[0], z0c[0]);
         z0r[0] = z0p[0] != nullptr;
         const double r1known = (cfg->inner_norm == 1) ? bs.last_res : -1.0;   // the CG's own final ||R1||
         if (r1known >= 0.0) {
@@ -1214,6 +1215,7 @@ int pph_pc_apply(pph_ctx* ctx, int which, int pc_type, int mg_smooth, const doub
   if (!ctx) return PPH_ERR_INVALID;
   PPH_REQUIRE(ctx, r_host && z_host, "NULL vector");
   PPH_TRY(pc_apply_prepare(ctx, which, &pc_type));
+  ctx->n_dict_dinv = 0;   // (counts this application's launches, as a solve's)
   const int64_t n = ctx->n;
   DevBuf<double> r, z, w;
   PPH_TRY(r.alloc(ctx, (size_t)n));
