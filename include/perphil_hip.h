@@ -372,6 +372,34 @@ int pph_eval_points(pph_ctx* ctx, const double* nodal_host, int ncomp, const dou
 int pph_eval_points_device(pph_ctx* ctx, const double* nodal_dev, int ncomp, const double* x_dev, int64_t m, double tol,
                            double* val_dev, double* grad_dev, int64_t* n_outside);
 
+/* Pathlines and travel times (perphil_amd/csrc/pph_trace.hip; no reference counterpart: the reference draws fd.quiver of the
+ * projected velocity, src/perphil/utils/postprocessing.py:34-63): m particles carried by v(x) = scale * u_h(x), u_h the CG-1
+ * vector field u [n][dim] (node-major, what pph_darcy_velocity writes) of the context's degree-1 mesh, from the seeds x0
+ * [m][dim].  A mesh is enough (no Dirichlet data, no assembled system); single context.  Classical RK4, fixed step dt > 0,
+ * fp64, points located by pph_eval_points' rule.  INSIDE: every coordinate in [0, 1] (NaN is outside; no tolerance).
+ * A step from x: k1 = v(x); |k1|_2 <= min_speed ends the particle (status 2).  x2 = x + dt/2 k1, x3 = x + dt/2 k2,
+ * x4 = x + dt k3, xn = x + dt/6 (k1 + 2 k2 + 2 k3 + k4); all four inside: x = xn, time += dt, length += |xn - x|_2.  Otherwise the
+ * exit step from x along k1: theta = min_e d_e / |k1_e| over k1_e != 0, d_e the distance to the face k1_e points at (lowest
+ * direction on a tie); theta <= dt: x += theta k1, that coordinate set to exactly 0 or 1, time += theta, length += theta |k1|,
+ * status 1 with the side numbered as pph_boundary_flux numbers sides; theta > dt: the Euler step x = clamp(x + dt k1, 0, 1),
+ * time += dt, length += the distance moved, and the particle goes on.  Every step counts in steps; a particle at max_steps
+ * ends with status 0.  A seed that is not inside: status 3, 0 steps, NaN end / time / length.
+ * status[p] = status | side << 8 (side 0 unless exited).  counts [4] (host): particles per status.  record_every = r > 0 and
+ * path not NULL: path[j][p][:] = position after j r steps, j = 0 .. max_steps / r; slots a particle never reaches hold NaN.
+ * One launch advances the live particles by at most `chunk` steps and compacts the survivors; no output depends on chunk
+ * or on the run: two calls give the same bits.  m <= 2^31 - 1; m == 0 is valid.  PPH_ERR_INVALID with a message: no mesh,
+ * world != 1, a degree-2 context, dt not finite or <= 0, scale zero or not finite, max_steps < 1, chunk < 1, record_every < 0,
+ * min_speed < 0 or NaN, NULL buffers with m > 0.  The host variant uploads, runs the device variant and copies back; the
+ * device variant works on caller-owned device arrays on the context stream and returns after the stream has finished. */
+int pph_trace_pathlines(pph_ctx* ctx, const double* u_host, double scale, const double* x0_host, int64_t m, double dt,
+                        int32_t max_steps, double min_speed, int32_t chunk, int32_t record_every, double* end_host,
+                        double* time_host, double* length_host, int32_t* steps_host, int32_t* status_host, double* path_host,
+                        int64_t* counts);
+int pph_trace_pathlines_device(pph_ctx* ctx, const double* u_dev, double scale, const double* x0_dev, int64_t m, double dt,
+                               int32_t max_steps, double min_speed, int32_t chunk, int32_t record_every, double* end_dev,
+                               double* time_dev, double* length_dev, int32_t* steps_dev, int32_t* status_dev, double* path_dev,
+                               int64_t* counts);
+
 /* ---- mass balance (post-processing; perphil_amd/csrc/pph_flux.hip) --------------------------------------------
  * No reference counterpart: the reference stops at pressures and a projected velocity.  These stand beside
  * calculate_darcy_velocity_from_pressure() (reference src/perphil/utils/postprocessing.py:34-63: the same flux

@@ -44,6 +44,7 @@ EXPORTS = [
     "pph_integrate", "pph_integrate_device", "pph_boundary_flux", "pph_boundary_flux_device",
     "pph_dpp_nodal_flux", "pph_dpp_nodal_flux_device",
     "pph_extreme_eigenvalues", "pph_tridiag_extremes", "pph_preconditioned_extremes",
+    "pph_trace_pathlines", "pph_trace_pathlines_device",
 ]
 
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64)
@@ -198,6 +199,10 @@ def _load() -> C.CDLL:
         "pph_extreme_eigenvalues": ([p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, f64p], C.c_int),
         "pph_tridiag_extremes": ([C.c_void_p, C.c_void_p, C.c_int, f64p], C.c_int),
         "pph_preconditioned_extremes": ([p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, f64p], C.c_int),
+        "pph_trace_pathlines": ([p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_double, C.c_int32,
+                                 C.c_int32] + [C.c_void_p] * 6 + [i64p], C.c_int),
+        "pph_trace_pathlines_device": ([p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_double,
+                                        C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [i64p], C.c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = ABI mismatch: fail loudly
@@ -597,6 +602,33 @@ class Context:
         self.torch_waits()
         return val, grad, int(nout.value)
 
+    def trace_pathlines_device(self, nodal, seeds, scale: float, dt: float, max_steps: int, min_speed: float = 0.0,
+                               chunk: int = 4096, record_every: int = 0):
+        """trace_pathlines on device tensors: nodal [n * dim], seeds [m, dim] -> (end [m, dim], time [m], length [m],
+        steps [m] int32, status [m] int32 (status | side << 8), path [n_rec, m, dim] or None, counts [4]); tensors on the
+        device.  Nothing but the counts moves to the host."""
+        import torch
+
+        nodal = self._device_in(nodal, self.n * self.dim, "nodal velocity")
+        if not (isinstance(seeds, torch.Tensor) and seeds.dtype == torch.float64 and seeds.is_cuda and seeds.dim() == 2
+                and seeds.shape[1] == self.dim and seeds.is_contiguous() and seeds.device.index == self.device):
+            raise ValueError(f"seeds must be a contiguous float64 tensor [m, {self.dim}] on cuda:{self.device}")
+        m = seeds.shape[0]
+        n_rec = int(max_steps) // int(record_every) + 1 if record_every > 0 else 0
+        end = self._device_out(m * self.dim).reshape(m, self.dim)
+        time, length = self._device_out(m), self._device_out(m)
+        steps = torch.empty(m, dtype=torch.int32, device=self.torch_device())
+        status = torch.empty(m, dtype=torch.int32, device=self.torch_device())
+        path = self._device_out(n_rec * m * self.dim).reshape(n_rec, m, self.dim) if n_rec else None
+        self.wait_for_torch()
+        counts = (C.c_int64 * 4)()
+        self._check(lib.pph_trace_pathlines_device(self._h, _tptr(nodal), float(scale), _tptr(seeds), int(m), float(dt),
+                                                   int(max_steps), float(min_speed), int(chunk), int(record_every), _tptr(end),
+                                                   _tptr(time), _tptr(length), _tptr(steps), _tptr(status),
+                                                   _tptr(path) if n_rec else None, counts))
+        self.torch_waits()
+        return end, time, length, steps, status, path, list(counts)
+
     # -- mass balance (pph_flux.hip): a NumPy array is uploaded for the call, a device tensor is read where it is ----
     def _nodal_arg(self, nodal, n: int, name: str):
         if isinstance(nodal, np.ndarray):
@@ -764,6 +796,29 @@ class Context:
         self._check(lib.pph_eval_points(self._h, _ptr(nodal), int(ncomp), _ptr(points), int(m), float(tol), _ptr(val),
                                         _ptr(grad), C.byref(nout)))
         return val, grad, int(nout.value)
+
+    def trace_pathlines(self, nodal: np.ndarray, seeds: np.ndarray, scale: float, dt: float, max_steps: int,
+                        min_speed: float = 0.0, chunk: int = 4096, record_every: int = 0):
+        """Pathlines of v = scale * u_h, u_h the CG-1 vector field nodal [n * dim] (node-major), from seeds [m, dim]
+        (pph_trace_pathlines): (end [m, dim], time [m], length [m], steps [m] int32, status [m] int32 (status | side << 8),
+        path [n_rec, m, dim] or None, counts [4])."""
+        nodal = np.ascontiguousarray(nodal, dtype=np.float64).reshape(-1)
+        seeds = np.ascontiguousarray(seeds, dtype=np.float64)
+        if nodal.shape != (self.n * self.dim,):
+            raise ValueError(f"expected {self.n * self.dim} nodal values, got {nodal.shape}")
+        if seeds.ndim != 2 or seeds.shape[1] != self.dim:
+            raise ValueError(f"seeds must have shape [m, {self.dim}], got {seeds.shape}")
+        m = seeds.shape[0]
+        n_rec = int(max_steps) // int(record_every) + 1 if record_every > 0 else 0
+        end = np.empty((m, self.dim), dtype=np.float64)
+        time, length = np.empty(m, dtype=np.float64), np.empty(m, dtype=np.float64)
+        steps, status = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.int32)
+        path = np.empty((n_rec, m, self.dim), dtype=np.float64) if n_rec else None
+        counts = (C.c_int64 * 4)()
+        self._check(lib.pph_trace_pathlines(self._h, _ptr(nodal), float(scale), _ptr(seeds), int(m), float(dt), int(max_steps),
+                                            float(min_speed), int(chunk), int(record_every), _ptr(end), _ptr(time), _ptr(length),
+                                            _ptr(steps), _ptr(status), _ptr(path), counts))
+        return end, time, length, steps, status, path, list(counts)
 
     def quadrature_points(self, nq: int, cell_begin: int, cell_count: int) -> np.ndarray:
         """Physical coordinates [cell_count * nq**dim, dim] of the Gauss points of a cell range (pph_quadrature_points)."""

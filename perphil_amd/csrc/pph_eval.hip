@@ -4,7 +4,7 @@
 // on the structured meshes, for CG-1 and degree-2 (pph_p2.h) fields on all four cell kinds.  One thread per point,
 // grid-stride; no search structure: the meshes are uniform boxes, so locating a point is arithmetic.
 //
-// Location rule.  Per direction e: t_e = x_e n_e (ONE rounding; everything after it is exact up to the basis evaluation),
+// Location rule (the code is pph_locate.h's, shared with pph_trace.hip).  Per direction e: t_e = x_e n_e (ONE rounding; everything after it is exact up to the basis evaluation),
 // box index c_e = clamp(floor(t_e), 0, n_e - 1), box-local coordinate xi_e = t_e - c_e (exact).  The point is OUTSIDE when
 // some xi_e lies outside [-tol, 1 + tol] (tol in box-local units; NaN coordinates are outside): every output of the point
 // is NaN and the point is counted.  An inside point is clamped to [0, 1].
@@ -22,61 +22,9 @@
 // Components: u[node * ncomp + c] (node-major, the CG-1 vector space's layout; a scalar field is ncomp = 1).  The point is
 // located and the basis evaluated once, then reused for every component.  No LDS: every thread gathers its own cell.
 #include "pph_internal.h"
+#include "pph_locate.h"
 #include "pph_p2.h"
 #include <cmath>
-
-// Kuhn sub-cell s: axes (a, b, c) of its path 0 -> 7, and the path position of its local vertex r (= the number of
-// set bits of the box corner p2_simplex_vertex(TET, s, r))
-__device__ static inline int tet_axis(int s, int k) {
-  const int A[6][3] = {{0, 1, 2}, {0, 2, 1}, {2, 0, 1}, {1, 0, 2}, {2, 1, 0}, {1, 2, 0}};
-  return A[s][k];
-}
-__device__ static inline int tet_pos(int s, int r) {
-  const int P[6][4] = {{0, 1, 2, 3}, {0, 1, 3, 2}, {0, 2, 3, 1}, {0, 2, 1, 3}, {0, 2, 1, 3}, {0, 1, 2, 3}};
-  return P[s][r];
-}
-
-// sub-cell of the box-local point xi, barycentric coordinates lam[r] of the sub-cell's local vertices and their
-// (constant) derivatives D[r][e] = d lam_r / d xi_e
-template <int KIND>
-__device__ static inline int simplex_locate(const double* xi, double* lam, double (*D)[3]) {
-  if constexpr (KIND == PPH_CELL_TRI) {
-    const bool lower = xi[0] + xi[1] <= 1.0;
-    if (lower) {
-      lam[0] = 1.0 - xi[0] - xi[1]; lam[1] = xi[0]; lam[2] = xi[1];
-      D[0][0] = -1.0; D[0][1] = -1.0; D[1][0] = 1.0; D[1][1] = 0.0; D[2][0] = 0.0; D[2][1] = 1.0;
-      return 0;
-    }
-    lam[0] = 1.0 - xi[1]; lam[1] = xi[0] + xi[1] - 1.0; lam[2] = 1.0 - xi[0];
-    D[0][0] = 0.0; D[0][1] = -1.0; D[1][0] = 1.0; D[1][1] = 1.0; D[2][0] = -1.0; D[2][1] = 0.0;
-    return 1;
-  } else {
-    int s = 5;
-#pragma unroll
-    for (int q = 4; q >= 0; --q)
-      if (xi[tet_axis(q, 0)] >= xi[tet_axis(q, 1)] && xi[tet_axis(q, 1)] >= xi[tet_axis(q, 2)]) s = q;
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-      if (q != s) continue;
-      const int a = tet_axis(q, 0), b = tet_axis(q, 1), c = tet_axis(q, 2);
-      const double lp[4] = {1.0 - xi[a], xi[a] - xi[b], xi[b] - xi[c], xi[c]};
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int k = tet_pos(q, r);
-        lam[r] = lp[k];
-#pragma unroll
-        for (int e = 0; e < 3; ++e)
-          D[r][e] = (k == 0) ? (e == a ? -1.0 : 0.0)
-                  : (k == 1) ? (e == a ? 1.0 : (e == b ? -1.0 : 0.0))
-                  : (k == 2) ? (e == b ? 1.0 : (e == c ? -1.0 : 0.0))
-                             : (e == c ? 1.0 : 0.0);
-      }
-    }
-    return s;
-  }
-}
-
-struct EvalGeo { int n[3]; };   // boxes per direction
 
 template <int KIND, int DEG, bool GRAD>
 __global__ __launch_bounds__(256) void k_eval_points(const int32_t* __restrict__ cells, const double* __restrict__ u,
@@ -96,9 +44,8 @@ __global__ __launch_bounds__(256) void k_eval_points(const int32_t* __restrict__
     bool out = false;
 #pragma unroll
     for (int e = 0; e < DIM; ++e) {
-      const double t = x[p * DIM + e] * (double)g.n[e];
-      const double c = fmin(fmax(floor(t), 0.0), (double)(g.n[e] - 1));   // (NaN -> 0)
-      const double s = t - c;
+      double c;
+      const double s = box_locate(x[p * DIM + e], g.n[e], &c);
       out = out || !(s >= -tol && s <= 1.0 + tol);
       xi[e] = fmin(fmax(s, 0.0), 1.0);
       box += stride * (int64_t)c;
@@ -124,9 +71,7 @@ __global__ __launch_bounds__(256) void k_eval_points(const int32_t* __restrict__
         for (int e = 0; e < DIM; ++e) { w[e][0] = 1.0 - xi[e]; w[e][1] = xi[e]; }
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
-          double nv = w[0][b & 1] * w[1][(b >> 1) & 1];
-          if constexpr (DIM == 3) nv *= w[2][(b >> 2) & 1];
-          N[b] = nv;
+          N[b] = q1_shape<DIM>(w, b);
           if constexpr (GRAD) {
 #pragma unroll
             for (int e = 0; e < DIM; ++e) {

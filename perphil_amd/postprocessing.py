@@ -292,3 +292,134 @@ def mass_balance(solution: fd.Function, params) -> MassBalance:
     mu = float(params.mu)
     direct = (boundary_fluxes(p1, float(params.k1) / mu), boundary_fluxes(p2, float(params.k2) / mu))
     return MassBalance(T, out, direct, (out[0] + T, out[1] - T))
+
+
+# -- pathlines -----------------------------------------------------------------------------------------------------------
+# Particles carried by v = scale * u_h, u_h a Function on the CG-1 vector space (``pph_trace.hip``: RK4 with a fixed step,
+# one lane per particle, the whole batch kept on the device until every particle has ended).  Sides are numbered as above.
+# Every check of the arguments comes before the first use of a context.
+
+@dataclass(frozen=True)
+class Pathlines:
+    """Where a batch of particles went.  ``end [m, dim]``: last position (on the boundary, coordinate exact, for an exited
+    particle).  ``time [m]``, ``length [m]``: travel time and arc length up to there.  ``steps [m]``: steps taken.
+    ``status [m]``: ``STEP_LIMIT``, ``EXITED``, ``STAGNANT`` (speed <= ``min_speed``) or ``OUTSIDE`` (the seed was not in the
+    unit square / cube: NaN end, time and length).  ``side [m]``: the side an exited particle left through (0 otherwise).
+    ``paths``: None, or ``[m, n_rec, dim]`` - the position after ``j * record_every`` steps, NaN once the particle has ended
+    (a transposed view of the kernel's ``[n_rec, m, dim]``).  ``counts``: particles per status name.  Arrays are NumPy
+    arrays, or torch tensors on the device when the seeds or the velocity were there."""
+    end: object
+    time: object
+    length: object
+    steps: object
+    status: object
+    side: object
+    paths: object
+    counts: Dict[str, int]
+
+    STEP_LIMIT = 0
+    EXITED = 1
+    STAGNANT = 2
+    OUTSIDE = 3
+
+
+_STATUS_NAMES = ("step_limit", "exited", "stagnant", "outside")
+
+
+def _trace_arguments(mesh, seeds, dt, max_steps, porosity, min_speed, record_every, chunk):
+    """The checks of trace_pathlines that need no velocity (travel_times makes them before it projects one): the seeds as
+    an array / device tensor [m, dim], whether they are on the device, and the numbers in their types."""
+    dim = mesh.dim
+    if mesh.distributed:
+        raise NotImplementedError("pathlines are implemented for single-context meshes: build the mesh with comm=fd.COMM_SELF")
+    dt, porosity, min_speed = float(dt), float(porosity), float(min_speed)
+    if not (np.isfinite(dt) and dt > 0.0):
+        raise ValueError(f"dt must be finite and positive, got {dt}")
+    if int(max_steps) != max_steps or not 1 <= int(max_steps) < 2 ** 31:
+        raise ValueError(f"max_steps must be an integer in [1, 2^31), got {max_steps}")
+    if not (np.isfinite(porosity) and porosity > 0.0):
+        raise ValueError(f"porosity must be finite and positive, got {porosity}")
+    if not min_speed >= 0.0:
+        raise ValueError(f"min_speed must not be negative or NaN, got {min_speed}")
+    if int(record_every) != record_every or not 0 <= int(record_every) < 2 ** 31:
+        raise ValueError(f"record_every must be a non-negative integer, got {record_every}")
+    if int(chunk) != chunk or not 1 <= int(chunk) < 2 ** 31:
+        raise ValueError(f"chunk must be an integer of at least 1, got {chunk}")
+    max_steps, record_every, chunk = int(max_steps), int(record_every), int(chunk)
+    dev_seeds = fd._is_tensor(seeds) and seeds.is_cuda
+    if fd._is_tensor(seeds):
+        import torch
+
+        if seeds.dtype != torch.float64:
+            raise ValueError(f"seeds must be float64, got {seeds.dtype}")
+        pts = seeds if dev_seeds else seeds.detach().numpy()
+    else:
+        pts = np.asarray(seeds)
+        if pts.dtype.kind not in "fiu":
+            raise ValueError(f"seeds must be real numbers, got dtype {pts.dtype}")
+        pts = pts.astype(np.float64, copy=False)
+    if pts.ndim == 1 and tuple(pts.shape) == (dim,):
+        pts = pts.reshape(1, dim)
+    if pts.ndim != 2 or pts.shape[1] != dim:
+        raise ValueError(f"seeds must be one point of {dim} coordinates or have shape [m, {dim}], got {tuple(pts.shape)}")
+    return pts, dev_seeds, dt, max_steps, porosity, min_speed, record_every, chunk
+
+
+def trace_pathlines(velocity: fd.Function, seeds, dt: float, max_steps: int, *, porosity: float = 1.0,
+                    backward: bool = False, min_speed: float = 0.0, record_every: int = 0, chunk: int = 4096) -> Pathlines:
+    """Pathlines of the seepage velocity ``velocity / porosity`` (``backward``: of its negative, towards the inflow) from
+    ``seeds`` - ``[m, dim]`` as a NumPy array or torch tensor, or one point - by RK4 with the fixed step ``dt``, at most
+    ``max_steps`` steps per particle (``pph_trace_pathlines``; the step rule is documented in include/perphil_hip.h).
+    ``velocity``: a Function on the CG-1 ``VectorFunctionSpace`` of a single-context mesh, e.g. what
+    ``calculate_darcy_velocity_from_pressure`` returns.  Device seeds or a device-resident velocity keep everything on the
+    device (the result fields are then CUDA tensors); host inputs give NumPy arrays.  ``chunk``: steps per launch between two
+    compactions of the live particles; no result depends on it.  The default leaves paths of up to 4096 steps to one launch:
+    on the measured workloads ("Pathlines") every compaction cost more than the idle lanes it removed."""
+    V = velocity.function_space()
+    mesh = V.mesh()
+    if not isinstance(V, fd.VectorFunctionSpace) or getattr(V, "degree", 1) != 1 or V.value_size != mesh.dim:
+        raise ValueError(f"trace_pathlines needs a Function on the CG-1 vector space of its mesh (VectorFunctionSpace(mesh, "
+                         f"'CG', 1)), got one on a {type(V).__name__} of degree {getattr(V, 'degree', '?')}")
+    pts, dev_seeds, dt, max_steps, porosity, min_speed, record_every, chunk = _trace_arguments(
+        mesh, seeds, dt, max_steps, porosity, min_speed, record_every, chunk)
+    scale = (-1.0 if backward else 1.0) / porosity
+    ctx = mesh.context()
+    if dev_seeds or velocity.on_device:
+        import torch
+
+        u = _device_field(velocity, ctx)
+        x = pts if dev_seeds else torch.from_numpy(np.array(pts, dtype=np.float64)).to(ctx.torch_device())   # (a copy: read-only arrays too)
+        end, time, length, steps, packed, path, counts = ctx.trace_pathlines_device(
+            u.contiguous().reshape(-1), x.contiguous(), scale, dt, max_steps, min_speed, chunk, record_every)
+        status, side = packed & 0xFF, packed >> 8
+        if path is not None:
+            path = path.permute(1, 0, 2)
+        if not dev_seeds:
+            end, time, length, steps, status, side = (a.cpu().numpy() for a in (end, time, length, steps, status, side))
+            path = None if path is None else path.cpu().numpy()
+    else:
+        end, time, length, steps, packed, path, counts = ctx.trace_pathlines(
+            velocity.vector(), np.ascontiguousarray(pts), scale, dt, max_steps, min_speed, chunk, record_every)
+        status, side = packed & 0xFF, packed >> 8
+        if path is not None:
+            path = path.transpose(1, 0, 2)
+    return Pathlines(end, time, length, steps, status, side, path, dict(zip(_STATUS_NAMES, (int(c) for c in counts))))
+
+
+def travel_times(pressure: fd.Function, conductivity, seeds, dt: float, max_steps: int, **kw) -> Pathlines:
+    """``trace_pathlines`` of ``calculate_darcy_velocity_from_pressure(pressure, conductivity)``: with ``porosity`` the times
+    are seepage travel times of that network, with ``backward=True`` times since the inflow.  A degree-2 pressure is refused,
+    as its velocity is."""
+    unknown = set(kw) - {"porosity", "backward", "min_speed", "record_every", "chunk"}
+    if unknown:
+        raise TypeError(f"travel_times got unexpected keyword arguments {sorted(unknown)}")
+    V = pressure.function_space()
+    if isinstance(V, (fd.MixedFunctionSpace, fd.VectorFunctionSpace)):
+        raise ValueError(f"travel_times needs a pressure on a scalar CG-1 space (its velocity lives on the CG-1 vector space), "
+                         f"got a Function on a {type(V).__name__}")
+    if getattr(V, "degree", 1) != 1:
+        raise NotImplementedError("the Darcy velocity of a degree-2 pressure is not implemented (the traced field lives on the "
+                                  "CG-1 vector space)")
+    _trace_arguments(V.mesh(), seeds, dt, max_steps, kw.get("porosity", 1.0), kw.get("min_speed", 0.0),
+                     kw.get("record_every", 0), kw.get("chunk", 4096))
+    return trace_pathlines(calculate_darcy_velocity_from_pressure(pressure, conductivity), seeds, dt, max_steps, **kw)
