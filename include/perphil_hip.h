@@ -429,6 +429,37 @@ int pph_boundary_flux_device(pph_ctx* ctx, const double* nodal_dev, double condu
 int pph_dpp_nodal_flux(pph_ctx* ctx, double k1, double k2, double beta, double mu, const double* p_host, double* r_host);
 int pph_dpp_nodal_flux_device(pph_ctx* ctx, double k1, double k2, double beta, double mu, const double* p_dev, double* r_dev);
 
+/* ---- adjoint solves and parameter gradients (perphil_amd/csrc/pph_adjoint.hip) ----------------------------------
+ * No reference counterpart: the reference solves for given k1, k2, beta, mu (src/perphil/solvers/solver.py:30-76) and cannot say
+ * how an output changes with them.  The operator of dpp_form (src/perphil/forms/dpp.py:95-132) is symmetric, so the adjoint of a
+ * functional J(p) with g = dJ/dp solves the same assembled system for another right-hand side, F A F lambda = F g (F zeroes the
+ * constrained dofs), and with the un-eliminated K and M
+ *   dJ/dk1 = -o0 / mu, dJ/dk2 = -o1 / mu, dJ/dbeta = -o2 / mu, dJ/dmu = (k1 o0 + k2 o1 + beta o2) / mu^2 (= lambda^T A p: 0 at a
+ *   converged solution), dJ/d(boundary value at constrained dof d) = g_d - (A_unel lambda)_d (pph_dpp_nodal_flux of lambda),
+ *   o0 = lambda1^T K p1, o1 = lambda2^T K p2, o2 = (lambda1 - lambda2)^T M (p1 - p2).
+ *
+ * pph_solve_rhs*: x = solution of F A F x = F b for the system of the last pph_assemble_dpp; b, x: 2n values, field-major.  The
+ * entries of b on constrained dofs are ignored (masked with the context's Dirichlet masks on the device), x is exactly 0 there.
+ * cfg, its checks, the solver paths, info and hist are those of pph_solve_device, whose loops run unchanged: the call exchanges
+ * the CONTENTS of the context's right-hand side, lifting (zero) and solution with saved copies, runs that solve and puts the
+ * contents back - buffer addresses do not change (captured graphs hold them), and on return the context's right-hand side, lifting
+ * and current solution hold the bits they held before: a pph_solve_device afterwards returns the bits it would have returned
+ * without the call.  A right-hand side that is zero on every free dof gives x = 0, iterations = 0, converged = 1 without entering
+ * a Krylov loop.  PPH_ERR_INVALID with a message: no assembled system, world != 1, a NULL buffer, b == x.  Memory: three vectors
+ * of 2n, released on return. */
+int pph_solve_rhs_device(pph_ctx* ctx, const pph_solver_cfg* cfg, const double* b_dev /* 2n */, double* x_dev /* 2n */,
+                         pph_solve_info* info, double* hist, int hist_cap);
+int pph_solve_rhs(pph_ctx* ctx, const pph_solver_cfg* cfg, const double* b_host, double* x_host, pph_solve_info* info,
+                  double* hist, int hist_cap);
+/* out = {o0, o1, o2} above, as integrals of the finite-element functions: int grad lambda1 . grad p1, int grad lambda2 . grad p2,
+ * int (lambda1 - lambda2)(p1 - p2); lam, p: 2n values, field-major.  One matrix-free pass over the cells (closed-form element
+ * forms of the uniform boxes): four nodal fields and the dof map are read once, nothing of K or M is built or stored.  Works on
+ * whichever mesh the context holds (CG-1 or degree 2, all four cell kinds), needs neither Dirichlet data nor an assembled system.
+ * fp64, no floating-point atomics: two calls give the same bits, and so do the host and the device variant.  PPH_ERR_INVALID with
+ * a message: no mesh, world != 1, a NULL buffer. */
+int pph_dpp_bilinear_device(pph_ctx* ctx, const double* lam_dev /* 2n */, const double* p_dev /* 2n */, double* out /* [3], host */);
+int pph_dpp_bilinear(pph_ctx* ctx, const double* lam_host, const double* p_host, double* out /* [3], host */);
+
 /* ---- multi-GPU communication hooks -------------------------------------------------------------
  * replaces: PETSc's implicit VecScatter halo exchange and VecDot all-reduce under mpiexec (never run in
  * the reference).  One context per rank holds one cell slab (pph_mesh_build with

@@ -11,6 +11,8 @@ reference module                              ->  here
 ``perphil.solvers.parameters``                    ``perphil_amd.solver_parameters``
 ``perphil.utils.manufactured_solutions``          ``perphil_amd.manufactured_solutions``
 ``firedrake`` objects crossing the boundary       ``perphil_amd.fd``
+(none: adjoint solves, parameter gradients,       ``perphil_amd.adjoint``
+ a solve torch autograd passes through)
 
 Importing the package does not touch the GPU; the HIP library is loaded on first use of
 ``perphil_amd.solver`` / ``perphil_amd._ffi`` and there is no CPU fallback.

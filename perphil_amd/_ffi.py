@@ -45,6 +45,7 @@ EXPORTS = [
     "pph_dpp_nodal_flux", "pph_dpp_nodal_flux_device",
     "pph_extreme_eigenvalues", "pph_tridiag_extremes", "pph_preconditioned_extremes",
     "pph_trace_pathlines", "pph_trace_pathlines_device",
+    "pph_solve_rhs", "pph_solve_rhs_device", "pph_dpp_bilinear", "pph_dpp_bilinear_device",
 ]
 
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64)
@@ -203,6 +204,11 @@ def _load() -> C.CDLL:
                                  C.c_int32] + [C.c_void_p] * 6 + [i64p], C.c_int),
         "pph_trace_pathlines_device": ([p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_double,
                                         C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [i64p], C.c_int),
+        "pph_solve_rhs": ([p, C.POINTER(SolverCfg), C.c_void_p, C.c_void_p, C.POINTER(SolveInfo), C.c_void_p, C.c_int], C.c_int),
+        "pph_solve_rhs_device": ([p, C.POINTER(SolverCfg), C.c_void_p, C.c_void_p, C.POINTER(SolveInfo), C.c_void_p, C.c_int],
+                                 C.c_int),
+        "pph_dpp_bilinear": ([p, C.c_void_p, C.c_void_p, f64p], C.c_int),
+        "pph_dpp_bilinear_device": ([p, C.c_void_p, C.c_void_p, f64p], C.c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = ABI mismatch: fail loudly
@@ -666,6 +672,38 @@ class Context:
         r = np.empty(2 * self.n, dtype=np.float64)
         self._check(lib.pph_dpp_nodal_flux(self._h, float(k1), float(k2), float(beta), float(mu), ptr, _ptr(r)))
         return r
+
+    # -- adjoint (pph_adjoint.hip): a NumPy array is uploaded for the call, a device tensor is read where it is ----
+    def solve_rhs(self, cfg: SolverCfg, b, hist_cap: int = 0, raise_on_diverged: bool = True):
+        """x with F A F x = F b for the assembled system (pph_solve_rhs / pph_solve_rhs_device): b a 2n array or device
+        tensor, x of the same kind (0 on constrained dofs).  Returns (x, info, hist) as solve() does; the context's own
+        right-hand side and solution are left as they were."""
+        keep, ptr, dev = self._nodal_arg(b, 2 * self.n, "right-hand side")
+        info = SolveInfo()
+        hist = np.zeros(max(hist_cap, 1), dtype=np.float64)
+        if dev:
+            x = self._device_out(2 * self.n)
+            st = lib.pph_solve_rhs_device(self._h, C.byref(cfg), ptr, _tptr(x), C.byref(info), _ptr(hist), int(hist_cap))
+            self.torch_waits()
+        else:
+            x = np.empty(2 * self.n, dtype=np.float64)
+            st = lib.pph_solve_rhs(self._h, C.byref(cfg), ptr, _ptr(x), C.byref(info), _ptr(hist), int(hist_cap))
+        self.last_info = info
+        self._check(st, allow_diverged=not raise_on_diverged)
+        nh = min(hist_cap, info.iterations + 1)
+        return x, info, hist[:nh].copy()
+
+    def dpp_bilinear(self, lam, p) -> tuple:
+        """(o0, o1, o2) = (lam1^T K p1, lam2^T K p2, (lam1 - lam2)^T M (p1 - p2)) of two mixed fields (2n values each,
+        field-major; arrays or device tensors), in one matrix-free pass (pph_dpp_bilinear / pph_dpp_bilinear_device)."""
+        keep_l, lptr, ldev = self._nodal_arg(lam, 2 * self.n, "adjoint field")
+        keep_p, pptr, pdev = self._nodal_arg(p, 2 * self.n, "mixed field")
+        if ldev != pdev:
+            raise ValueError("dpp_bilinear: both fields must be arrays or both device tensors")
+        out = (C.c_double * 3)()
+        fn = lib.pph_dpp_bilinear_device if ldev else lib.pph_dpp_bilinear
+        self._check(fn(self._h, lptr, pptr, out))
+        return out[0], out[1], out[2]
 
     # -- export -------------------------------------------------------------------------------
     def csr(self, which: int):

@@ -807,6 +807,8 @@ int pph_eig_lanczos(pph_ctx* ctx, const Csr& A, double tol, int max_it, int chec
 // block, 1 the A22 block; pc_apply_prepare checks the pairing, resolves PPH_PC_PMG at degree 1 and builds the hierarchy / the
 // CSR values; pc_apply_device: z = B r (dinv_work: n doubles, used by PPH_PC_JACOBI)
 int pc_apply_prepare(pph_ctx* ctx, int which, int* pc_type);
+// the checks pph_solve_device makes of a configuration against the context (pph_solve.hip)
+int validate_cfg(pph_ctx* ctx, const pph_solver_cfg* cfg);
 int pc_apply_device(pph_ctx* ctx, int which, int pc_type, int ns, const double* r, double* z, double* dinv_work);
 // a symmetric preconditioner B of one operator of the context, set up once and applied many times (pph_solve.hip; the
 // preconditioned Lanczos iteration of pph_eig.hip).  which: pph_get_csr's selector (0 monolithic, 2 M, 3 A11, 4 A22)

@@ -733,7 +733,7 @@ __global__ void k_add2(double* __restrict__ out, const double* __restrict__ a, c
     out[i] = a[i] + b[i];
 }
 
-static int validate_cfg(pph_ctx* ctx, const pph_solver_cfg* cfg) {
+int validate_cfg(pph_ctx* ctx, const pph_solver_cfg* cfg) {   // (also pph_solve_rhs*, pph_adjoint.hip)
   PPH_REQUIRE(ctx, cfg != nullptr, "solver cfg is NULL");
   PPH_REQUIRE(ctx, cfg->ksp_type >= PPH_KSP_PREONLY && cfg->ksp_type <= PPH_KSP_GMRES, "unknown ksp_type %d",
               cfg->ksp_type);
