@@ -183,6 +183,17 @@ int pph_set_dirichlet_device(pph_ctx* ctx, int field, const int64_t* nodes, cons
  * A12 = A21^T = -(beta/mu)M and the lifted right-hand side.  `monolithic != 0` additionally
  * materialises the 2n x 2n field-major CSR. */
 int pph_assemble_dpp(pph_ctx* ctx, double k1, double k2, double beta, double mu, int monolithic);
+/* The same system with PER-FIELD mass coefficients (no reference counterpart; the operator of a theta time step, below):
+ *   A11 = (k1/mu) K + (beta/mu + sigma1) M,   A22 = (k2/mu) K + (beta/mu + sigma2) M,   A12 = A21^T = -(beta/mu) M,
+ * Dirichlet-eliminated as above, lifted right-hand side -F A_shifted,unel u0.  sigma_f must be finite and >= 0 (PPH_ERR_INVALID
+ * with a message otherwise); sigma = (0, 0) IS pph_assemble_dpp: the same kernels, the same bits.  With a sigma != 0: single
+ * context only; the fused assembly takes the tile / two-pass kernels (the node kernel forms one mass coefficient for the three
+ * blocks), the shift's share -sigma_f F M g_f of the lifting is one matrix-free product behind the fused kernels (inside the
+ * two-step path's own lifting kernel otherwise), and every level of the multigrid hierarchies (PPH_PC_MG, PPH_PC_PMG,
+ * PPH_PC_CMG: d_ff = coefK_f K_ii + (beta/mu + sigma_f) M_ii, coupling -(beta/mu) M) is built with the coefficients of its
+ * field.  Every assembly invalidates hierarchies and factorisations: a change of sigma is a new system. */
+int pph_assemble_dpp_shifted(pph_ctx* ctx, double k1, double k2, double beta, double mu, double sigma1, double sigma2,
+                             int monolithic);
 
 /* ---- solve --------------------------------------------------------------------------------
  * replaces: LinearVariationalSolver.solve() -> KSPSolve (reference src/perphil/solvers/solver.py:67-71);
@@ -459,6 +470,47 @@ int pph_solve_rhs(pph_ctx* ctx, const pph_solver_cfg* cfg, const double* b_host,
  * a message: no mesh, world != 1, a NULL buffer. */
 int pph_dpp_bilinear_device(pph_ctx* ctx, const double* lam_dev /* 2n */, const double* p_dev /* 2n */, double* out /* [3], host */);
 int pph_dpp_bilinear(pph_ctx* ctx, const double* lam_host, const double* p_host, double* out /* [3], host */);
+
+/* ---- transient DPP: the right-hand side of a theta step (perphil_amd/csrc/pph_transient.hip) ---------------------
+ * No reference counterpart: the reference solves the steady state of dpp_form (src/perphil/forms/dpp.py:95-132).  With a storage
+ * coefficient S_f > 0 per network,
+ *   S1 dp1/dt - div(k1/mu grad p1) + beta/mu (p1 - p2) = 0,   S2 dp2/dt - div(k2/mu grad p2) - beta/mu (p1 - p2) = 0,
+ * the theta scheme (1/2 <= theta <= 1) in delta form solves (Sigma M / dt + theta A) d = -F A_unel p^n, p^{n+1} = p^n + d, where
+ * A_unel is the operator of pph_dpp_nodal_flux and F zeroes the dofs the context's Dirichlet sets constrain.  These calls form
+ *   b = -F A_unel p:   b1 = -F1 ((k1/mu) K p1 + (beta/mu) M (p1 - p2)),   b2 = -F2 ((k2/mu) K p2 - (beta/mu) M (p1 - p2))
+ * for both fields in one pass; p, b: 2n values, field-major; the entries of b on constrained dofs are exactly 0.  A mesh is enough
+ * (no assembled system); without Dirichlet data F is the identity.  Degree-1 meshes: matrix-free - one work item per node gathers
+ * from its incident cells with the closed-form element matrices of the canonical cell, cells outside the box skipped by index
+ * arithmetic; neither K nor M is stored and the dof map is not read.  Degree 2, or option "asm_uniform" 0: the CSR walk of
+ * pph_dpp_nodal_flux on the stored K and M, then mask and sign.  fp64, no floating-point atomics: two calls give the same bits.
+ * PPH_ERR_INVALID with a message: no mesh, world != 1, a NULL buffer, p == b, mu == 0.  The host variant copies in and out; the
+ * device variant works on caller-owned device arrays on the context stream and returns after the stream has finished with them. */
+int pph_dpp_step_rhs_device(pph_ctx* ctx, double k1, double k2, double beta, double mu, const double* p_dev /* 2n */,
+                            double* b_dev /* 2n */);
+int pph_dpp_step_rhs(pph_ctx* ctx, double k1, double k2, double beta, double mu, const double* p_host, double* b_host);
+/* The step loop.  pph_transient_begin checks S_f > 0, dt > 0, 1/2 <= theta <= 1 (backward Euler 1, Crank-Nicolson 1/2), assembles
+ * the step operator Sigma M / dt + theta A through pph_assemble_dpp_shifted(theta k1, theta k2, theta beta, mu, S1 / dt, S2 / dt,
+ * monolithic) and records the steady coefficients.  pph_transient_steps* advances p (2n values, field-major, in / out) by up to
+ * nsteps steps: the constrained entries of p are first overwritten with the context's Dirichlet values; the CONTENTS of the
+ * context's right-hand side, lifting and solution are exchanged with saved copies ONCE per call, as pph_solve_rhs does per solve
+ * (addresses unchanged; on return they hold the bits they held before); per step the kernel above writes b_s = -F A_unel p^s
+ * straight into the context's right-hand side, the solve loop of pph_solve_device runs on the path cfg names (same checks), and
+ * one kernel does p += d and leaves the partial sums of ||d||^2.  norms[s] = {||b_s||_2, ||d_s||_2}; infos[s]: the solve of
+ * step s (either may be NULL).  A step whose right-hand side is zero on every free dof takes no solve (d = 0, iterations 0,
+ * converged 1).  The loop stops before step s when ||b_s|| <= steady_tol ||b_0|| (steady_tol <= 0: never; b_0: the first right-hand side
+ * formed after pph_transient_begin, so that a run split over several calls stops where one call would); *steps_done = steps
+ * taken.  No allocation per step; per step the host reads ||b_s||^2 (with it ||d_{s-1}||^2) once, beside the solve's own
+ * synchronisations.  A diverged solve ends the loop with PPH_ERR_DIVERGED: p holds the last completed step, *steps_done is set.
+ * PPH_ERR_INVALID with a message: steps before begin; an assembly or a change of the Dirichlet sets in between; world != 1; a NULL
+ * buffer (p, cfg, steps_done); nsteps < 1; bad S, dt, theta.  Memory: three vectors of 2n, released on return.  The host variant
+ * copies p in and out. */
+int pph_transient_begin(pph_ctx* ctx, double k1, double k2, double beta, double mu, double S1, double S2, double theta, double dt,
+                        int monolithic);
+int pph_transient_steps_device(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_dev /* 2n, in/out */, int nsteps,
+                               double steady_tol, pph_solve_info* infos /* [nsteps] or NULL */,
+                               double* norms /* [nsteps][2] or NULL */, int* steps_done);
+int pph_transient_steps(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_host /* 2n, in/out */, int nsteps, double steady_tol,
+                        pph_solve_info* infos, double* norms, int* steps_done);
 
 /* ---- multi-GPU communication hooks -------------------------------------------------------------
  * replaces: PETSc's implicit VecScatter halo exchange and VecDot all-reduce under mpiexec (never run in

@@ -13,6 +13,7 @@ reference module                              ->  here
 ``firedrake`` objects crossing the boundary       ``perphil_amd.fd``
 (none: adjoint solves, parameter gradients,       ``perphil_amd.adjoint``
  a solve torch autograd passes through)
+(none: storage terms, theta time stepping)        ``perphil_amd.solve_dpp_transient`` / ``TransientSolution``
 
 Importing the package does not touch the GPU; the HIP library is loaded on first use of
 ``perphil_amd.solver`` / ``perphil_amd._ffi`` and there is no CPU fallback.
@@ -27,7 +28,7 @@ from .manufactured_solutions import exact_expressions, exact_expressions_3d, int
 __all__ = [
     "fd", "solver_parameters", "DPPParameters", "create_mesh", "create_function_spaces", "dpp_form",
     "dpp_delayed_form", "dpp_splitted_form", "exact_expressions", "exact_expressions_3d", "interpolate_exact",
-    "solve_dpp", "solve_dpp_nonlinear", "Solution",
+    "solve_dpp", "solve_dpp_nonlinear", "Solution", "solve_dpp_transient", "TransientSolution",
 ]
 
 
@@ -40,4 +41,9 @@ def __getattr__(name):
 
         mod = importlib.import_module(".solver" if name != "_ffi" else "._ffi", __name__)
         return mod if name in ("solver", "_ffi") else getattr(mod, name)
+    if name in ("solve_dpp_transient", "TransientSolution", "transient"):
+        import importlib
+
+        mod = importlib.import_module(".transient", __name__)
+        return mod if name == "transient" else getattr(mod, name)
     raise AttributeError(name)

@@ -46,6 +46,8 @@ EXPORTS = [
     "pph_extreme_eigenvalues", "pph_tridiag_extremes", "pph_preconditioned_extremes",
     "pph_trace_pathlines", "pph_trace_pathlines_device",
     "pph_solve_rhs", "pph_solve_rhs_device", "pph_dpp_bilinear", "pph_dpp_bilinear_device",
+    "pph_dpp_step_rhs", "pph_dpp_step_rhs_device", "pph_assemble_dpp_shifted",
+    "pph_transient_begin", "pph_transient_steps", "pph_transient_steps_device",
 ]
 
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64)
@@ -209,6 +211,14 @@ def _load() -> C.CDLL:
                                  C.c_int),
         "pph_dpp_bilinear": ([p, C.c_void_p, C.c_void_p, f64p], C.c_int),
         "pph_dpp_bilinear_device": ([p, C.c_void_p, C.c_void_p, f64p], C.c_int),
+        "pph_dpp_step_rhs": ([p] + [C.c_double] * 4 + [C.c_void_p, C.c_void_p], C.c_int),
+        "pph_dpp_step_rhs_device": ([p] + [C.c_double] * 4 + [C.c_void_p, C.c_void_p], C.c_int),
+        "pph_assemble_dpp_shifted": ([p] + [C.c_double] * 6 + [C.c_int], C.c_int),
+        "pph_transient_begin": ([p] + [C.c_double] * 8 + [C.c_int], C.c_int),
+        "pph_transient_steps": ([p, C.POINTER(SolverCfg), C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                 C.POINTER(C.c_int)], C.c_int),
+        "pph_transient_steps_device": ([p, C.POINTER(SolverCfg), C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_int)], C.c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = ABI mismatch: fail loudly
@@ -415,8 +425,15 @@ class Context:
         return (old[0].shape == nodes.shape and old[1].shape == vals.shape and torch.equal(old[0], nodes)
                 and torch.equal(old[1], vals))
 
-    def assemble(self, k1: float, k2: float, beta: float, mu: float, monolithic: bool = True) -> None:
-        self._check(lib.pph_assemble_dpp(self._h, float(k1), float(k2), float(beta), float(mu), int(monolithic)))
+    def assemble(self, k1: float, k2: float, beta: float, mu: float, monolithic: bool = True, sigma=(0.0, 0.0)) -> None:
+        """Assembles the eliminated blocks and the lifted right-hand side; ``sigma`` = (sigma1, sigma2) adds sigma_f M to the
+        diagonal block of field f (pph_assemble_dpp_shifted; (0, 0) is pph_assemble_dpp itself)."""
+        s1, s2 = (float(v) for v in sigma)
+        if s1 == 0.0 and s2 == 0.0:
+            self._check(lib.pph_assemble_dpp(self._h, float(k1), float(k2), float(beta), float(mu), int(monolithic)))
+        else:
+            self._check(lib.pph_assemble_dpp_shifted(self._h, float(k1), float(k2), float(beta), float(mu), s1, s2,
+                                                     int(monolithic)))
 
     # -- result vectors ---------------------------------------------------------------------
     # Large results land in page-locked host arrays: the device-to-host copy then runs at PCIe speed and no fresh pages
@@ -704,6 +721,55 @@ class Context:
         fn = lib.pph_dpp_bilinear_device if ldev else lib.pph_dpp_bilinear
         self._check(fn(self._h, lptr, pptr, out))
         return out[0], out[1], out[2]
+
+    # -- transient (pph_transient.hip): a NumPy array is uploaded for the call, a device tensor is read where it is ----
+    def step_rhs(self, p, k1: float, k2: float, beta: float, mu: float):
+        """b = -F A_unel p, the right-hand side of a theta step in delta form, for the mixed field p (2n values,
+        field-major): minus ``dpp_nodal_flux(p)`` with exact zeros on the dofs the Dirichlet sets constrain.  An array for
+        an array, a new device tensor for a device tensor (pph_dpp_step_rhs / pph_dpp_step_rhs_device); matrix-free on
+        degree-1 meshes."""
+        keep, ptr, dev = self._nodal_arg(p, 2 * self.n, "mixed field")
+        if dev:
+            b = self._device_out(2 * self.n)
+            self._check(lib.pph_dpp_step_rhs_device(self._h, float(k1), float(k2), float(beta), float(mu), ptr, _tptr(b)))
+            self.torch_waits()
+            return b
+        b = np.empty(2 * self.n, dtype=np.float64)
+        self._check(lib.pph_dpp_step_rhs(self._h, float(k1), float(k2), float(beta), float(mu), ptr, _ptr(b)))
+        return b
+
+    def transient_begin(self, k1: float, k2: float, beta: float, mu: float, storage, theta: float, dt: float,
+                        monolithic: bool = True) -> None:
+        """Assembles the operator Sigma M / dt + theta A of a theta step (storage = (S1, S2) > 0, 1/2 <= theta <= 1, dt > 0)
+        and records the steady coefficients for ``transient_steps`` (pph_transient_begin)."""
+        S1, S2 = (float(v) for v in storage)
+        self._check(lib.pph_transient_begin(self._h, float(k1), float(k2), float(beta), float(mu), S1, S2, float(theta),
+                                            float(dt), int(monolithic)))
+
+    def transient_steps(self, cfg: SolverCfg, p, nsteps: int, steady_tol: float = 0.0, raise_on_diverged: bool = True):
+        """Advances the mixed field p (2n values, field-major) by up to `nsteps` theta steps IN PLACE: a float64 NumPy array
+        (copied in and out) or a device tensor (pph_transient_steps / pph_transient_steps_device).  Returns (steps_done,
+        infos [steps_done] of SolveInfo, norms [steps_done, 2] = (||b_s||, ||d_s||))."""
+        nsteps = int(nsteps)
+        infos = (SolveInfo * max(nsteps, 1))()
+        norms = np.zeros((max(nsteps, 1), 2), dtype=np.float64)
+        done = C.c_int(0)
+        if isinstance(p, np.ndarray):
+            if p.dtype != np.float64 or p.shape != (2 * self.n,) or not p.flags.c_contiguous or not p.flags.writeable:
+                raise ValueError(f"transient_steps: p must be a writeable contiguous float64 array of {2 * self.n} values")
+            st = lib.pph_transient_steps(self._h, C.byref(cfg), _ptr(p), nsteps, float(steady_tol), infos, _ptr(norms),
+                                         C.byref(done))
+        else:
+            t = self._device_in(p, 2 * self.n, "mixed field")
+            if t.data_ptr() != p.data_ptr():
+                raise ValueError("transient_steps: p must be a contiguous float64 device tensor (it is advanced in place)")
+            st = lib.pph_transient_steps_device(self._h, C.byref(cfg), _tptr(t), nsteps, float(steady_tol), infos, _ptr(norms),
+                                                C.byref(done))
+            self.torch_waits()
+        k = int(done.value)
+        self.last_info = infos[k - 1] if k > 0 else SolveInfo()
+        self._check(st, allow_diverged=not raise_on_diverged)
+        return k, [infos[i] for i in range(k)], norms[:k].copy()
 
     # -- export -------------------------------------------------------------------------------
     def csr(self, which: int):

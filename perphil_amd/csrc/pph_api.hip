@@ -1,6 +1,7 @@
 // C-ABI entry points of libperphil_hip.so (see include/perphil_hip.h for the contract and the
 // reference interfaces each one replaces).
 #include "pph_internal.h"
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -405,13 +406,19 @@ int pph_get_stream(pph_ctx* ctx, void** stream) {
 }
 
 // ---- assembly -----------------------------------------------------------------------------------
-int pph_assemble_dpp(pph_ctx* ctx, double k1, double k2, double beta, double mu, int monolithic) {
-  if (!ctx) return PPH_ERR_INVALID;
+static int assemble_dpp(pph_ctx* ctx, const char* who, double k1, double k2, double beta, double mu, double sigma1, double sigma2,
+                        int monolithic) {
   PPH_HIP(ctx, hipSetDevice(ctx->device));
-  PPH_REQUIRE(ctx, ctx->mesh_ok, "pph_assemble_dpp before pph_mesh_build");
+  PPH_REQUIRE(ctx, ctx->mesh_ok, "%s before pph_mesh_build", who);
   PPH_REQUIRE(ctx, k1 > 0 && k2 > 0 && mu > 0 && beta >= 0, "need k1, k2, mu > 0 and beta >= 0");
+  PPH_REQUIRE(ctx, std::isfinite(sigma1) && std::isfinite(sigma2) && sigma1 >= 0 && sigma2 >= 0,
+              "%s: sigma1, sigma2 must be finite and >= 0, got %g, %g", who, sigma1, sigma2);
+  const bool shifted = sigma1 != 0.0 || sigma2 != 0.0;
+  PPH_REQUIRE(ctx, !shifted || ctx->world == 1, "%s: per-field mass coefficients are implemented for single-context meshes", who);
   release_system(ctx);
+  ctx->asm_epoch++;
   ctx->a = k1 / mu; ctx->b = beta / mu; ctx->c = k2 / mu;
+  ctx->sig[0] = sigma1; ctx->sig[1] = sigma2;
   float ms = 0.f;
   if (!ctx->mesh.km_valid && pph_can_fuse_assembly(ctx)) {
     // integration needed anyway: element rows, then one node-centred pass straight to the eliminated blocks
@@ -419,6 +426,8 @@ int pph_assemble_dpp(pph_ctx* ctx, double k1, double k2, double beta, double mu,
     // pph_get_timers - a failing kernel surfaces at the solve's first fetch)
     PPH_HIP(ctx, hipEventRecord(ctx->ev_asm0, ctx->stream));
     PPH_TRY(pph_launch_assemble_fused(ctx, monolithic));
+    // the fused epilogues lift with M (g1 - g2) only; the shift's share -sigma_f F M g_f: one matrix-free product behind them
+    if (shifted) PPH_TRY(pph_step_lift(ctx, sigma1, sigma2, ctx->g[0].p, ctx->g[1].p, ctx->rhs.p));
     PPH_HIP(ctx, hipEventRecord(ctx->ev_asm1, ctx->stream));
     ctx->asm_time_pending = true;
     ctx->t_bc = 0.0;
@@ -445,6 +454,17 @@ int pph_assemble_dpp(pph_ctx* ctx, double k1, double k2, double beta, double mu,
   PPH_HIP(ctx, hipGetLastError());
   ctx->asm_ok = true;
   return PPH_OK;
+}
+
+int pph_assemble_dpp(pph_ctx* ctx, double k1, double k2, double beta, double mu, int monolithic) {
+  if (!ctx) return PPH_ERR_INVALID;
+  return assemble_dpp(ctx, "pph_assemble_dpp", k1, k2, beta, mu, 0.0, 0.0, monolithic);
+}
+
+int pph_assemble_dpp_shifted(pph_ctx* ctx, double k1, double k2, double beta, double mu, double sigma1, double sigma2,
+                             int monolithic) {
+  if (!ctx) return PPH_ERR_INVALID;
+  return assemble_dpp(ctx, "pph_assemble_dpp_shifted", k1, k2, beta, mu, sigma1, sigma2, monolithic);
 }
 
 // ---- export -------------------------------------------------------------------------------------

@@ -850,7 +850,7 @@ __global__ __launch_bounds__(256) void k_gather_rows(const int32_t* __restrict__
         } else {
           if (fa.keep_km) { K[k] = kv; M[k] = mv; }
           const bool diag = (j == (int32_t)node);
-          double o11 = fa.a * kv + fa.b * mv, o22 = fa.c * kv + fa.b * mv, o12 = -fa.b * mv, o21 = o12;
+          double o11 = fa.a * kv + fa.b1 * mv, o22 = fa.c * kv + fa.b2 * mv, o12 = -fa.b * mv, o21 = o12;
           if (near) {
             // same arithmetic as k_lift_rhs / k_blocks: ghost rows empty, Dirichlet rows identity, constrained columns zero
             const uint8_t cm1 = fa.m1[j], cm2 = fa.same ? cm1 : fa.m2[j];
@@ -1034,7 +1034,7 @@ __global__ __launch_bounds__(256) void k_asm_simplex_gather(const int32_t* __res
           const int32_t jc = cl[q];
           if (fa.keep_km) { K[s + q] = kv; M[s + q] = mv; }
           const bool diag = (jc == (int32_t)node);
-          double o11 = fa.a * kv + fa.b * mv, o22 = fa.c * kv + fa.b * mv, o12 = -fa.b * mv, o21 = o12;
+          double o11 = fa.a * kv + fa.b1 * mv, o22 = fa.c * kv + fa.b2 * mv, o12 = -fa.b * mv, o21 = o12;
           if (near) {
             const uint8_t cm1 = fa.m1[jc], cm2 = fa.same ? cm1 : fa.m2[jc];
             if (fa.rhs) {
@@ -1198,11 +1198,14 @@ __global__ __launch_bounds__(256) void k_row_near(Stencil st, int px, int py, in
   }
 }
 
+// SHIFT: per-field mass coefficients (pph_assemble_dpp_shifted): also M g1 and M g2, whose sigma_f-fold joins the lifting; the
+// unshifted instantiation is the kernel as it was
+template <bool SHIFT>
 __global__ __launch_bounds__(256) void k_lift_rhs(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                   const double* __restrict__ K, const double* __restrict__ M,
                                                   const uint8_t* __restrict__ m1, const uint8_t* __restrict__ m2,
                                                   const double* __restrict__ g1, const double* __restrict__ g2,
-                                                  double a, double b, double c, int64_t n,
+                                                  double a, double b, double c, double sg1, double sg2, int64_t n,
                                                   const uint8_t* __restrict__ rownear,
                                                   double* __restrict__ rhs, double* __restrict__ u0) {
   const int sub = threadIdx.x % BC_LANES;
@@ -1212,22 +1215,29 @@ __global__ __launch_bounds__(256) void k_lift_rhs(const int64_t* __restrict__ ro
       if (sub == 0) { rhs[row] = 0.0; rhs[n + row] = 0.0; u0[row] = 0.0; u0[n + row] = 0.0; }
       continue;
     }
-    double sK1 = 0, sK2 = 0, sM = 0;
+    double sK1 = 0, sK2 = 0, sM = 0, sM1 = 0, sM2 = 0;   // (sM1, sM2: M g_f, the shifted system's share of the lifting)
     for (int64_t k = rowptr[row] + sub; k < rowptr[row + 1]; k += BC_LANES) {
       const int32_t j = col[k];
       const double v1 = g1[j], v2 = g2[j];
       const double kk = K[k], mm = M[k];
       sK1 += kk * v1; sK2 += kk * v2; sM += mm * (v1 - v2);
+      if (SHIFT) { sM1 += mm * v1; sM2 += mm * v2; }
     }
 #pragma unroll
     for (int o = BC_LANES / 2; o > 0; o >>= 1) {
       sK1 += __shfl_down(sK1, o, BC_LANES);
       sK2 += __shfl_down(sK2, o, BC_LANES);
       sM += __shfl_down(sM, o, BC_LANES);
+      if (SHIFT) { sM1 += __shfl_down(sM1, o, BC_LANES); sM2 += __shfl_down(sM2, o, BC_LANES); }
     }
     if (sub == 0) {
-      rhs[row] = (m1[row] != 0) ? 0.0 : -(a * sK1 + b * sM);
-      rhs[n + row] = (m2[row] != 0) ? 0.0 : -(c * sK2 - b * sM);
+      if (SHIFT) {
+        rhs[row] = (m1[row] != 0) ? 0.0 : -((a * sK1 + b * sM) + sg1 * sM1);
+        rhs[n + row] = (m2[row] != 0) ? 0.0 : -((c * sK2 - b * sM) + sg2 * sM2);
+      } else {
+        rhs[row] = (m1[row] != 0) ? 0.0 : -(a * sK1 + b * sM);
+        rhs[n + row] = (m2[row] != 0) ? 0.0 : -(c * sK2 - b * sM);
+      }
       u0[row] = g1[row];
       u0[n + row] = g2[row];
     }
@@ -1241,7 +1251,7 @@ __global__ __launch_bounds__(256) void k_lift_rhs(const int64_t* __restrict__ ro
 __global__ __launch_bounds__(256) void k_blocks(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                 const double* __restrict__ K, const double* __restrict__ M,
                                                 const uint8_t* __restrict__ m1, const uint8_t* __restrict__ m2,
-                                                double a, double b, double c, int64_t n,
+                                                double a, double b, double c, double b1, double b2, int64_t n,
                                                 const uint8_t* __restrict__ rownear, double* __restrict__ A11,
                                                 double* __restrict__ A22, double* __restrict__ A12,
                                                 double* __restrict__ A21) {
@@ -1258,10 +1268,10 @@ __global__ __launch_bounds__(256) void k_blocks(const int64_t* __restrict__ rowp
         const double kk4[4] = {k01.x, k01.y, k23.x, k23.y};
         const double mm4[4] = {q01.x, q01.y, q23.x, q23.y};
         if (base >= s && base + 3 < e) {
-          *reinterpret_cast<double2*>(A11 + base) = make_double2(a * kk4[0] + b * mm4[0], a * kk4[1] + b * mm4[1]);
-          *reinterpret_cast<double2*>(A11 + base + 2) = make_double2(a * kk4[2] + b * mm4[2], a * kk4[3] + b * mm4[3]);
-          *reinterpret_cast<double2*>(A22 + base) = make_double2(c * kk4[0] + b * mm4[0], c * kk4[1] + b * mm4[1]);
-          *reinterpret_cast<double2*>(A22 + base + 2) = make_double2(c * kk4[2] + b * mm4[2], c * kk4[3] + b * mm4[3]);
+          *reinterpret_cast<double2*>(A11 + base) = make_double2(a * kk4[0] + b1 * mm4[0], a * kk4[1] + b1 * mm4[1]);
+          *reinterpret_cast<double2*>(A11 + base + 2) = make_double2(a * kk4[2] + b1 * mm4[2], a * kk4[3] + b1 * mm4[3]);
+          *reinterpret_cast<double2*>(A22 + base) = make_double2(c * kk4[0] + b2 * mm4[0], c * kk4[1] + b2 * mm4[1]);
+          *reinterpret_cast<double2*>(A22 + base + 2) = make_double2(c * kk4[2] + b2 * mm4[2], c * kk4[3] + b2 * mm4[3]);
           *reinterpret_cast<double2*>(A12 + base) = make_double2(-b * mm4[0], -b * mm4[1]);
           *reinterpret_cast<double2*>(A12 + base + 2) = make_double2(-b * mm4[2], -b * mm4[3]);
           if (A21) {
@@ -1272,8 +1282,8 @@ __global__ __launch_bounds__(256) void k_blocks(const int64_t* __restrict__ rowp
 #pragma unroll
           for (int t = 0; t < 4; ++t)
             if (base + t >= s && base + t < e) {
-              A11[base + t] = a * kk4[t] + b * mm4[t];
-              A22[base + t] = c * kk4[t] + b * mm4[t];
+              A11[base + t] = a * kk4[t] + b1 * mm4[t];
+              A22[base + t] = c * kk4[t] + b2 * mm4[t];
               A12[base + t] = -b * mm4[t];
               if (A21) A21[base + t] = -b * mm4[t];
             }
@@ -1299,8 +1309,8 @@ __global__ __launch_bounds__(256) void k_blocks(const int64_t* __restrict__ rowp
         const bool diag = (j == (int32_t)row);
         const bool c1 = (m1[j] & 1) != 0, c2 = same ? c1 : (m2[j] & 1) != 0;
         // ghost rows (bit 1) belong to the neighbouring slab: empty here; Dirichlet rows: identity
-        o11[t] = (r1 & 2) ? 0.0 : (r1 & 1) ? (diag ? 1.0 : 0.0) : (c1 ? 0.0 : a * kk + b * mm);
-        o22[t] = (r2 & 2) ? 0.0 : (r2 & 1) ? (diag ? 1.0 : 0.0) : (c2 ? 0.0 : c * kk + b * mm);
+        o11[t] = (r1 & 2) ? 0.0 : (r1 & 1) ? (diag ? 1.0 : 0.0) : (c1 ? 0.0 : a * kk + b1 * mm);
+        o22[t] = (r2 & 2) ? 0.0 : (r2 & 1) ? (diag ? 1.0 : 0.0) : (c2 ? 0.0 : c * kk + b2 * mm);
         o12[t] = (r1 != 0 || c2) ? 0.0 : -b * mm;
         o21[t] = (r2 != 0 || c1) ? 0.0 : -b * mm;
       }
@@ -1458,11 +1468,16 @@ int pph_launch_blocks(pph_ctx* ctx, int monolithic) {
   PPH_TRY(blocks_prepare(ctx, true));
   int64_t nb = ceil_div64(n * BC_LANES, 256);
   int grid = (int)(nb < 256 * 16 ? nb : 256 * 16);
-  hipLaunchKernelGGL(k_lift_rhs, dim3(grid), dim3(256), 0, ctx->stream, ctx->mesh.rowptr.p, ctx->mesh.col.p, ctx->mesh.K.p,
-                     ctx->mesh.M.p, ctx->bcmask[0].p, ctx->bcmask[1].p, ctx->g[0].p, ctx->g[1].p, ctx->a, ctx->b, ctx->c,
-                     n, ctx->rownear.p, ctx->rhs.p, ctx->u0.p);
+  if (ctx->sig[0] != 0.0 || ctx->sig[1] != 0.0)
+    hipLaunchKernelGGL(k_lift_rhs<true>, dim3(grid), dim3(256), 0, ctx->stream, ctx->mesh.rowptr.p, ctx->mesh.col.p, ctx->mesh.K.p,
+                       ctx->mesh.M.p, ctx->bcmask[0].p, ctx->bcmask[1].p, ctx->g[0].p, ctx->g[1].p, ctx->a, ctx->b, ctx->c,
+                       ctx->sig[0], ctx->sig[1], n, ctx->rownear.p, ctx->rhs.p, ctx->u0.p);
+  else
+    hipLaunchKernelGGL(k_lift_rhs<false>, dim3(grid), dim3(256), 0, ctx->stream, ctx->mesh.rowptr.p, ctx->mesh.col.p, ctx->mesh.K.p,
+                       ctx->mesh.M.p, ctx->bcmask[0].p, ctx->bcmask[1].p, ctx->g[0].p, ctx->g[1].p, ctx->a, ctx->b, ctx->c,
+                       ctx->sig[0], ctx->sig[1], n, ctx->rownear.p, ctx->rhs.p, ctx->u0.p);
   hipLaunchKernelGGL(k_blocks, dim3(grid), dim3(256), 0, ctx->stream, ctx->mesh.rowptr.p, ctx->mesh.col.p, ctx->mesh.K.p, ctx->mesh.M.p,
-                     ctx->bcmask[0].p, ctx->bcmask[1].p, ctx->a, ctx->b, ctx->c, n, ctx->rownear.p, ctx->A11.p, ctx->A22.p,
+                     ctx->bcmask[0].p, ctx->bcmask[1].p, ctx->a, ctx->b, ctx->c, ctx->bm(0), ctx->bm(1), n, ctx->rownear.p, ctx->A11.p, ctx->A22.p,
                      ctx->A12.p, ctx->a21_alias ? nullptr : ctx->A21.p);
   PPH_HIP(ctx, hipGetLastError());
   ctx->diag0_valid = false;
@@ -1959,7 +1974,7 @@ __global__ __launch_bounds__(512, 4) void k_asm_tile(const double* __restrict__ 
         }
         if (fa.keep_km) { K[kcsr] = kv; M[kcsr] = mv; }
         const bool diag = (slot == NSLOT / 2);
-        double o11 = fa.a * kv + fa.b * mv, o22 = fa.c * kv + fa.b * mv, o12 = -fa.b * mv, o21 = o12;
+        double o11 = fa.a * kv + fa.b1 * mv, o22 = fa.c * kv + fa.b2 * mv, o12 = -fa.b * mv, o21 = o12;
         if (near) {
           const uint8_t cm1 = fa.m1[j], cm2 = fa.same ? cm1 : fa.m2[j];
           if (fa.rhs) {
@@ -2935,8 +2950,12 @@ int pph_launch_fused_kernels(pph_ctx* ctx, MeshData& mesh, const FuseArgs& fa, d
   const bool multilinear = (mesh.kind == PPH_CELL_QUAD || mesh.kind == PPH_CELL_HEX);
   // CSR positions are needed for CSR output and for K / M; the simplex and two-pass gather kernels also walk the
   // pattern's columns (the node and tile kernels address neighbours in closed form)
+  // the node kernel forms b M once per entry for the three blocks: it serves ONE mass coefficient.  Per-field coefficients
+  // (pph_assemble_dpp_shifted with a sigma != 0, and the levels under it) take the tile / two-pass kernels, whose epilogues
+  // hold fa.b1, fa.b2 beside fa.b at the same operation count; with sigma = 0 nothing here changes
+  const bool one_mass = fa.b1 == fa.b && fa.b2 == fa.b;
   const bool closed_form = multilinear && ctx->asm_tile && !ctx->asm_ring &&
-                           ((ctx->asm_node && ctx->asm_affine && mesh.all_affine && !ctx->asm_tile_probe && mesh.n < ((int64_t)1 << 29)) ||
+                           ((one_mass && ctx->asm_node && ctx->asm_affine && mesh.all_affine && !ctx->asm_tile_probe && mesh.n < ((int64_t)1 << 29)) ||
                             ctx->asm_tile == 2 || mesh.n >= ctx->asm_tile_min_nodes);
   if (fa.ld == 0 || fa.keep_km || !closed_form) PPH_TRY(pph_ensure_pattern(ctx, mesh));
   // every path below writes every row of A11 .. A21 - except the check-mode node assembly that is allowed not to (nostore)
@@ -2961,7 +2980,7 @@ int pph_launch_fused_kernels(pph_ctx* ctx, MeshData& mesh, const FuseArgs& fa, d
     return PPH_OK;
   }
   // box meshes (every cell with equal parallel edges), stencil-ELL output: one thread per node, registers only
-  if (ctx->asm_node && ctx->asm_tile && ctx->asm_affine && mesh.all_affine && fa.ld != 0 && !fa.keep_km && !ctx->asm_tile_probe && !ctx->asm_ring &&
+  if (one_mass && ctx->asm_node && ctx->asm_tile && ctx->asm_affine && mesh.all_affine && fa.ld != 0 && !fa.keep_km && !ctx->asm_tile_probe && !ctx->asm_ring &&
       mesh.n < ((int64_t)1 << 29)) {
     const int64_t nb = ((ceil_div64(mesh.n, 256) + 7) / 8) * 8;
     const int grid = (int)(nb < 256 * 64 ? nb : 256 * 64);
@@ -3187,7 +3206,7 @@ int pph_launch_fused_kernels(pph_ctx* ctx, MeshData& mesh, const FuseArgs& fa, d
 // Dirichlet-eliminated operators coefK[f] K + coefM M (f = 0, 1) of a multigrid level straight from the element
 // rows, with the smoother's diagonal inverses and spectral bounds (no K/M, no coupling blocks, no lifting)
 int pph_launch_level_operators(pph_ctx* ctx, MeshData& mesh, const uint8_t* m1, const uint8_t* m2, const uint8_t* near,
-                               int same, double coefK1, double coefK2, double coefM, double* A1, double* A2,
+                               int same, double coefK1, double coefK2, double coefM1, double coefM2, double* A1, double* A2,
                                double* dinv1, double* dinv2, unsigned long long* lam, int64_t ell_ld, int ell_sym,
                                DictGroup* group, SellDict* dicts, const Sell* views, WaveMap* wmap, ValuesState* vstate) {
   FuseArgs fa;
@@ -3201,7 +3220,8 @@ int pph_launch_level_operators(pph_ctx* ctx, MeshData& mesh, const uint8_t* m1, 
   fa.symg = (ell_sym && ctx->world > 1) ? 1 : 0;
   fa.m1 = m1; fa.m2 = m2; fa.near = near;
   fa.g1 = nullptr; fa.g2 = nullptr;
-  fa.a = coefK1; fa.b = coefM; fa.c = coefK2;
+  fa.a = coefK1; fa.b = coefM1; fa.c = coefK2;
+  fa.b1 = coefM1; fa.b2 = coefM2;   // (no coupling block on a level: b only stands for the node kernel's one mass coefficient)
   fa.A11 = A1; fa.A22 = A2; fa.A12 = nullptr; fa.A21 = nullptr;
   fa.rhs = nullptr; fa.u0 = nullptr;
   fa.dinv1 = dinv1; fa.dinv2 = dinv2;
@@ -3236,6 +3256,7 @@ int pph_launch_assemble_fused(pph_ctx* ctx, int monolithic) {
   fa.m1 = ctx->bcmask[0].p; fa.m2 = ctx->bcmask[1].p; fa.near = ctx->rownear.p;
   fa.g1 = ctx->g[0].p; fa.g2 = ctx->g[1].p;
   fa.a = ctx->a; fa.b = ctx->b; fa.c = ctx->c;
+  fa.b1 = ctx->bm(0); fa.b2 = ctx->bm(1);
   if (ell) {
     fa.A11 = ctx->E11.p; fa.A22 = ctx->E22.p; fa.A12 = ctx->E12.p; fa.A21 = ctx->a21_alias ? nullptr : ctx->E21.p;
   } else {

@@ -58,7 +58,8 @@ __device__ __forceinline__ double cmg_group_sum(double v) {
 template <int G>
 __global__ __launch_bounds__(256) void k_cmg_setup(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                    const double* __restrict__ K, const double* __restrict__ M, int64_t n,
-                                                   double a, double b, double c, const uint8_t* __restrict__ m0,
+                                                   double a, double b, double c, double b1, double b2,
+                                                   const uint8_t* __restrict__ m0,
                                                    const uint8_t* __restrict__ m1, double* __restrict__ binv,
                                                    unsigned long long* __restrict__ lam, double* __restrict__ v11,
                                                    double* __restrict__ v22, double* __restrict__ v12,
@@ -75,8 +76,8 @@ __global__ __launch_bounds__(256) void k_cmg_setup(const int64_t* __restrict__ r
     kd = cmg_group_sum<G>(kd);
     md = cmg_group_sum<G>(md);
     const bool f0 = m0[row] != 0, f1 = m1[row] != 0;
-    const double d11 = f0 ? 1.0 : a * kd + b * md;
-    const double d22 = f1 ? 1.0 : c * kd + b * md;
+    const double d11 = f0 ? 1.0 : a * kd + b1 * md;   // (b1, b2 = b + sigma_f: the diagonal blocks' mass coefficients;
+    const double d22 = f1 ? 1.0 : c * kd + b2 * md;   //  s1 = d11 + d12 = a kd + sigma1 md >= 0 still holds, the coupling stays -b M)
     const double d12 = (f0 || f1) ? 0.0 : cb * md;
     const double s1 = d11 + d12, s2 = d22 + d12;
     const double det = s1 * s2 - d12 * (s1 + s2);
@@ -86,8 +87,8 @@ __global__ __launch_bounds__(256) void k_cmg_setup(const int64_t* __restrict__ r
       const int64_t j = col[k];
       const double kj = K[k], mj = M[k];
       const bool g0 = m0[j] != 0, g1 = m1[j] != 0;
-      const double a11 = f0 ? (j == row ? 1.0 : 0.0) : (g0 ? 0.0 : a * kj + b * mj);
-      const double a22 = f1 ? (j == row ? 1.0 : 0.0) : (g1 ? 0.0 : c * kj + b * mj);
+      const double a11 = f0 ? (j == row ? 1.0 : 0.0) : (g0 ? 0.0 : a * kj + b1 * mj);
+      const double a22 = f1 ? (j == row ? 1.0 : 0.0) : (g1 ? 0.0 : c * kj + b2 * mj);
       const double c12 = (f0 || g1) ? 0.0 : cb * mj;   // C_ij
       const double c21 = (f1 || g0) ? 0.0 : cb * mj;   // (C^T)_ij
       sa += fabs(i11 * a11 + i12 * c21) + fabs(i11 * c12 + i12 * a22);
@@ -293,7 +294,7 @@ void cmg_release(pph_ctx* ctx) {
 
 #define CMG_SETUP_GO(GG)                                                                                                   \
   hipLaunchKernelGGL(k_cmg_setup<GG>, dim3(cmg_grid(n, GG)), dim3(256), 0, ctx->stream, m.rowptr.p, m.col.p, C.Kp, C.Mp, n, \
-                     ctx->a, ctx->b, ctx->c, L.maskp[0], L.maskp[1], C.binv.p, ctx->cmg_lam.p + l, v[0], v[1], v[2], v[3])
+                     ctx->a, ctx->b, ctx->c, ctx->bm(0), ctx->bm(1), L.maskp[0], L.maskp[1], C.binv.p, ctx->cmg_lam.p + l, v[0], v[1], v[2], v[3])
 
 int cmg_setup(pph_ctx* ctx) {
   PPH_REQUIRE(ctx, ctx->world == 1, "pc_type pph_cmg: single context only (no slab decomposition)");

@@ -323,8 +323,9 @@ static int integrate_dev(pph_ctx* ctx, DevBuf<double>& part, const double* u, do
   return PPH_OK;
 }
 
-// K and M of the mesh (integrated on demand, kept by the mesh like the Darcy projection's) and the product kernel
-static int nodal_flux_dev(pph_ctx* ctx, double k1, double k2, double beta, double mu, const double* p, double* r) {
+// K and M of the mesh (integrated on demand, kept by the mesh like the Darcy projection's) and the product kernel, enqueued on
+// the context stream (also the CSR formulation of pph_transient.hip's step right-hand side)
+int pph_nodal_flux_launch(pph_ctx* ctx, double k1, double k2, double beta, double mu, const double* p, double* r) {
   MeshData& m = ctx->mesh;
   PPH_HIP(ctx, hipSetDevice(ctx->device));
   if (!m.km_valid) {
@@ -390,7 +391,7 @@ extern "C" int pph_dpp_nodal_flux_device(pph_ctx* ctx, double k1, double k2, dou
   if (!ctx) return PPH_ERR_INVALID;
   PPH_TRY(flux_check(ctx, "pph_dpp_nodal_flux_device", p_dev && r_dev));
   PPH_REQUIRE(ctx, mu != 0.0, "pph_dpp_nodal_flux_device: mu must not be 0");
-  PPH_TRY(nodal_flux_dev(ctx, k1, k2, beta, mu, p_dev, r_dev));
+  PPH_TRY(pph_nodal_flux_launch(ctx, k1, k2, beta, mu, p_dev, r_dev));
   PPH_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the caller's arrays are free again when the call returns)
   return PPH_OK;
 }
@@ -404,7 +405,7 @@ extern "C" int pph_dpp_nodal_flux(pph_ctx* ctx, double k1, double k2, double bet
   DevBuf<double> p, r;
   int st = upload(ctx, p, p_host, n2);
   if (st == PPH_OK) st = r.alloc(ctx, n2);
-  if (st == PPH_OK) st = nodal_flux_dev(ctx, k1, k2, beta, mu, p.p, r.p);
+  if (st == PPH_OK) st = pph_nodal_flux_launch(ctx, k1, k2, beta, mu, p.p, r.p);
   if (st == PPH_OK) {
     hipError_t e = hipMemcpyAsync(r_host, r.p, sizeof(double) * n2, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);

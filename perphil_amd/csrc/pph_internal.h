@@ -155,6 +155,7 @@ struct FuseArgs {
   const uint8_t *m1, *m2, *near;
   const double *g1, *g2;
   double a, b, c;
+  double b1 = 0, b2 = 0;           // mass coefficients of the DIAGONAL blocks: b + sigma_f (pph_assemble_dpp_shifted; b itself stays the coupling's)
   double *A11, *A22, *A12, *A21;   // A21 null: aliased to A12 (same Dirichlet set on both fields)
   double *rhs, *u0;                // [2n]
   double *dinv1, *dinv2;           // [n] each
@@ -414,6 +415,14 @@ struct pph_ctx {
   int ghost_lo = 0, ghost_hi = 0;
   int64_t n = 0, nnzb = 0;              // copies of mesh.n / mesh.nnzb
   bool mesh_ok = false, asm_ok = false, mono_ok = false;
+  uint64_t asm_epoch = 0;               // counts assemblies (the transient loop notices one in between)
+  // pph_transient_begin (pph_transient.hip): the steady coefficients k1, k2, beta, mu of the step right-hand side, and the
+  // assembly and Dirichlet sets the step operator belongs to
+  bool tr_on = false;
+  double tr_coef[4] = {0, 0, 0, 0};
+  double tr_b0 = -1.0;                  // ||b_0|| of the run (the first step after pph_transient_begin; < 0: not taken yet)
+  uint64_t tr_asm_epoch = 0;
+  int tr_bc_epoch = -1;
   DevBuf<uint8_t> bcmask[2];            // per field: 1 Dirichlet, 2 ghost, 0 free
   DevBuf<double> dinv0[2];              // fused assembly: 1 / diag of A11, A22 ...
   DevBuf<unsigned long long> lam0;      // ... and their spectral bounds (bit patterns), valid when diag0_valid
@@ -461,6 +470,8 @@ struct pph_ctx {
   DevBuf<int32_t> mcol;
   DevBuf<double> mval;
   double a = 0, b = 0, c = 0;           // k1/mu, beta/mu, k2/mu
+  double sig[2] = {0, 0};               // sigma_f of pph_assemble_dpp_shifted: A_ff = coefK_f K + (b + sigma_f) M (0: pph_assemble_dpp)
+  double bm(int f) const { return b + sig[f]; }   // mass coefficient of diagonal block f (sigma_f = 0: b + 0.0 is b, bit for bit; b >= 0)
 
   // multi-GPU: cell-slab decomposition along z; communication goes through two callbacks so that the
   // same solver code runs over torch.distributed (gloo in tests, nccl = RCCL on the 8-GPU node)
@@ -624,7 +635,7 @@ int pph_ensure_csr_blocks(pph_ctx* ctx);   // CSR values of A11, A22, A12 (, A21
 int pph_launch_assemble_fused(pph_ctx* ctx, int monolithic);
 // A1, A2: CSR value arrays (ell_ld == 0) or stencil-ELL arrays with leading dimension ell_ld
 int pph_launch_level_operators(pph_ctx* ctx, MeshData& mesh, const uint8_t* m1, const uint8_t* m2, const uint8_t* near,
-                               int same, double coefK1, double coefK2, double coefM, double* A1, double* A2,
+                               int same, double coefK1, double coefK2, double coefM1, double coefM2, double* A1, double* A2,
                                double* dinv1, double* dinv2, unsigned long long* lam, int64_t ell_ld, int ell_sym,
                                DictGroup* group = nullptr, SellDict* dicts = nullptr, const Sell* views = nullptr,
                                WaveMap* wmap = nullptr, ValuesState* vstate = nullptr);
@@ -800,6 +811,11 @@ double cmg_step_bytes(const pph_ctx* ctx);
 int cmg_step_bench(pph_ctx* ctx, int reps, double* ms_out);   // ms per fine-level pass of k_cmg_row (mode 0) alone
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// r = A_unel p on the stored K and M of the mesh (pph_flux.hip: the launch behind pph_dpp_nodal_flux_device, not waited for)
+int pph_nodal_flux_launch(pph_ctx* ctx, double k1, double k2, double beta, double mu, const double* p, double* r);
+// rhs[f] -= sigma_f F_f M g_f on a degree-1 mesh, matrix-free (pph_transient.hip: the shifted assembly's share of the lifting
+// behind the fused kernels); g1, g2: n values each, rhs: 2n, enqueued on the context stream
+int pph_step_lift(pph_ctx* ctx, double sigma1, double sigma2, const double* g1, const double* g2, double* rhs);
 // extreme eigenvalues of a symmetric operator by plain Lanczos (pph_eig.hip; out as pph_extreme_eigenvalues documents it)
 int pph_eig_lanczos(pph_ctx* ctx, const Csr& A, double tol, int max_it, int check_every, double* vec_lo, double* vec_hi,
                     double* out);

@@ -665,7 +665,7 @@ int mg_setup(pph_ctx* ctx) {
         }
         for (int f = 0; f < 2; ++f) PPH_TRY(L.dinv[f].alloc(ctx, (size_t)L.n));
         PPH_TRY(pph_launch_level_operators(ctx, m, L.maskp[0], L.maskp[1], L.rownear.p, ctx->a21_alias ? 1 : 0, coefK[0],
-                                           coefK[1], ctx->b, ell_only ? L.own_ell[0].p : L.own_val[0].p,
+                                           coefK[1], ctx->bm(0), ctx->bm(1), ell_only ? L.own_ell[0].p : L.own_val[0].p,
                                            ell_only ? L.own_ell[1].p : L.own_val[1].p, L.dinv[0].p, L.dinv[1].p,
                                            lamdev.p + 2 * l, ell_only ? L.ell[0].ld : 0, ell_only ? L.ell[0].sym : 0,
                                            ell_only ? &L.dgroup : nullptr, ell_only ? L.dict : nullptr, ell_only ? L.ell : nullptr,
@@ -682,7 +682,7 @@ int mg_setup(pph_ctx* ctx) {
         }
       } else {
         for (int f = 0; f < 2; ++f) {
-          pph_launch_scalar_block(ctx, m, L.maskp[f], coefK[f], ctx->b, L.own_val[f].p);
+          pph_launch_scalar_block(ctx, m, L.maskp[f], coefK[f], ctx->bm(f), L.own_val[f].p);
           if (use_ell) PPH_TRY(sell_from_csr(ctx, m, L.own_val[f].p, L.own_ell[f], &L.ell[f], pph_sell_sym_from_csr(ctx)));
           L.vals = ValuesState();   // (written completely, by another path)
         }
