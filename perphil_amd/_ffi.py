@@ -425,11 +425,13 @@ class Context:
         return (old[0].shape == nodes.shape and old[1].shape == vals.shape and torch.equal(old[0], nodes)
                 and torch.equal(old[1], vals))
 
-    def assemble(self, k1: float, k2: float, beta: float, mu: float, monolithic: bool = True, sigma=(0.0, 0.0)) -> None:
+    def assemble(self, k1: float, k2: float, beta: float, mu: float, monolithic: bool = True, sigma=(0.0, 0.0),
+                 shifted_entry: bool = False) -> None:
         """Assembles the eliminated blocks and the lifted right-hand side; ``sigma`` = (sigma1, sigma2) adds sigma_f M to the
-        diagonal block of field f (pph_assemble_dpp_shifted; (0, 0) is pph_assemble_dpp itself)."""
+        diagonal block of field f (pph_assemble_dpp_shifted; (0, 0) is pph_assemble_dpp itself, unless ``shifted_entry`` asks
+        for the shifted entry point whatever sigma is)."""
         s1, s2 = (float(v) for v in sigma)
-        if s1 == 0.0 and s2 == 0.0:
+        if s1 == 0.0 and s2 == 0.0 and not shifted_entry:
             self._check(lib.pph_assemble_dpp(self._h, float(k1), float(k2), float(beta), float(mu), int(monolithic)))
         else:
             self._check(lib.pph_assemble_dpp_shifted(self._h, float(k1), float(k2), float(beta), float(mu), s1, s2,
