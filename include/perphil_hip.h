@@ -512,6 +512,59 @@ int pph_transient_steps_device(pph_ctx* ctx, const pph_solver_cfg* cfg, double* 
 int pph_transient_steps(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_host /* 2n, in/out */, int nsteps, double steady_tol,
                         pph_solve_info* infos, double* norms, int* steps_done);
 
+/* pph_transient_steps with one more argument: traj, [nsteps + 1][2n].  Row 0 receives p after the Dirichlet values were written,
+ * row s + 1 the state after step s; rows past *steps_done + 1 are not written.  The device variant takes a caller-owned device
+ * array; p, norms, infos and the context are left bit for bit as pph_transient_steps leaves them. */
+int pph_transient_steps_record_device(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_dev /* 2n, in/out */, int nsteps,
+                                      double steady_tol, pph_solve_info* infos, double* norms, int* steps_done,
+                                      double* traj_dev /* [nsteps + 1][2n] */);
+int pph_transient_steps_record(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_host /* 2n, in/out */, int nsteps,
+                               double steady_tol, pph_solve_info* infos, double* norms, int* steps_done, double* traj_host);
+
+/* ---- transient adjoint (perphil_amd/csrc/pph_transient_adjoint.hip) ---------------------------------------------
+ * Gradients of J = sum_{s=0..N} j_s(p_s) over a trajectory of pph_transient_steps, G_s = dj_s/dp_s.  T = Sigma M / dt + theta A is
+ * symmetric: with q_N = F G_N, for s = N-1 down to 0
+ *   w_s = T^-1 q_{s+1};  pm = p_s + theta d_s, d_s = p_{s+1} - p_s;
+ *   terms[s] = {w1^T K pm1, w2^T K pm2, (w1 - w2)^T M (pm1 - pm2), w1^T M d1, w2^T M d2};
+ *   q_s = F G_s + q_{s+1} - F A_unel w_s;  Wsum += w_s,
+ * and with O_q = sum_s terms[s][q] (summed by the caller in the order s = N-1 down to 0)
+ *   dJ/dk1 = -O0/mu, dJ/dk2 = -O1/mu, dJ/dbeta = -O2/mu, dJ/dmu = (k1 O0 + k2 O1 + beta O2)/mu^2, dJ/dS1 = -O3/dt, dJ/dS2 = -O4/dt,
+ *   dJ/dp_0 = q_0 on free dofs, dJ/d(boundary value at constrained dof c) = sum_s (G_s)_c - (A_unel Wsum)_c (pph_dpp_nodal_flux).
+ *
+ * pph_transient_bilinear*: out5 = the five forms of ONE step for any w, p0 (= p_s), p1 (= p_{s+1}) (2n values each, field-major) in
+ * one matrix-free pass over the cells; a mesh is enough.  CG-1 and degree 2, all four cell kinds.  fp64, no atomics, the grid is a
+ * function of the mesh alone: two calls give the same bits, and so do the host and the device variant. */
+int pph_transient_bilinear_device(pph_ctx* ctx, const double* w_dev, const double* p0_dev, const double* p1_dev, double theta,
+                                  double* out5 /* [5], host */);
+int pph_transient_bilinear(pph_ctx* ctx, const double* w_host, const double* p0_host, const double* p1_host, double theta,
+                           double* out5 /* [5], host */);
+/* The transpose of pph_eval_points: out[node * ncomp + k] += sum_m phi_node(x_m) c[m * ncomp + k] (out is ADDED to).  Location rule,
+ * tie-breaks and tol are pph_eval_points'; a point outside contributes nothing and is counted in *n_outside.  One workgroup takes
+ * the points in index order (lanes: the local basis functions; a barrier between points): no floating-point atomics, bitwise
+ * reproducible, any number of points per cell, duplicates included.  The cost is LINEAR in m - the points are taken one after
+ * the other - which suits observation wells (tens to thousands of points), not fields of points. */
+int pph_eval_points_adjoint_device(pph_ctx* ctx, const double* x_dev /* [m][dim] */, int64_t m, const double* c_dev /* [m][ncomp] */,
+                                   int ncomp, double tol, double* out_dev /* [n][ncomp], in/out */, int64_t* n_outside);
+int pph_eval_points_adjoint(pph_ctx* ctx, const double* x_host, int64_t m, const double* c_host, int ncomp, double tol,
+                            double* out_host, int64_t* n_outside);
+/* The backward loop above on the step operator of the last pph_transient_begin (same epoch checks as pph_transient_steps).  traj:
+ * [N + 1][2n] as pph_transient_steps_record wrote it.  G_s = g[s] (g: [N + 1][2n], or NULL) + E^T obs_c[s] (obs_x: [m][dim],
+ * obs_c: [N + 1][m][2] = weights of (p1, p2) at the points, or NULL; points located with obs_tol as pph_eval_points does); at least
+ * one of g and obs_c must be given.  terms: [N][5] on the host, written on the device per step and fetched once at the end (rows
+ * of steps not reached are 0); q0: 2n; wsum: 2n or NULL; infos[s]: the solve of step s, or NULL.  *steps_done = backward steps
+ * completed.  The CONTENTS of the context's right-hand side, lifting and solution are exchanged once per call and put back bit for
+ * bit; the solve loop of pph_solve_device runs on the path cfg names; a q that is zero on every free dof takes no solve (w = 0).  Per
+ * step the host reads ||q||^2 once, beside the solve's own synchronisations.  A diverged solve ends the loop with
+ * PPH_ERR_DIVERGED (q0 then holds the last completed q).  Memory: seven vectors of 2n, released on return; the host variant also
+ * holds the trajectory and g on the device for the call. */
+int pph_transient_adjoint_device(pph_ctx* ctx, const pph_solver_cfg* cfg, const double* traj_dev, const double* g_dev,
+                                 const double* obs_x_dev, int64_t m, const double* obs_c_dev, double obs_tol, int nsteps,
+                                 double* terms /* [nsteps][5], host */, double* q0_dev, double* wsum_dev,
+                                 pph_solve_info* infos /* [nsteps] or NULL */, int* steps_done);
+int pph_transient_adjoint(pph_ctx* ctx, const pph_solver_cfg* cfg, const double* traj_host, const double* g_host,
+                          const double* obs_x_host, int64_t m, const double* obs_c_host, double obs_tol, int nsteps, double* terms,
+                          double* q0_host, double* wsum_host, pph_solve_info* infos, int* steps_done);
+
 /* ---- multi-GPU communication hooks -------------------------------------------------------------
  * replaces: PETSc's implicit VecScatter halo exchange and VecDot all-reduce under mpiexec (never run in
  * the reference).  One context per rank holds one cell slab (pph_mesh_build with

@@ -41,7 +41,8 @@ def __getattr__(name):
 
         mod = importlib.import_module(".solver" if name != "_ffi" else "._ffi", __name__)
         return mod if name in ("solver", "_ffi") else getattr(mod, name)
-    if name in ("solve_dpp_transient", "TransientSolution", "transient"):
+    if name in ("solve_dpp_transient", "TransientSolution", "transient", "transient_sensitivities", "TransientSensitivities",
+                "solve_dpp_transient_torch"):
         import importlib
 
         mod = importlib.import_module(".transient", __name__)

@@ -48,6 +48,9 @@ EXPORTS = [
     "pph_solve_rhs", "pph_solve_rhs_device", "pph_dpp_bilinear", "pph_dpp_bilinear_device",
     "pph_dpp_step_rhs", "pph_dpp_step_rhs_device", "pph_assemble_dpp_shifted",
     "pph_transient_begin", "pph_transient_steps", "pph_transient_steps_device",
+    "pph_transient_steps_record", "pph_transient_steps_record_device",
+    "pph_transient_bilinear", "pph_transient_bilinear_device", "pph_eval_points_adjoint", "pph_eval_points_adjoint_device",
+    "pph_transient_adjoint", "pph_transient_adjoint_device",
 ]
 
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64)
@@ -219,6 +222,18 @@ def _load() -> C.CDLL:
                                  C.POINTER(C.c_int)], C.c_int),
         "pph_transient_steps_device": ([p, C.POINTER(SolverCfg), C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                         C.POINTER(C.c_int)], C.c_int),
+        "pph_transient_steps_record": ([p, C.POINTER(SolverCfg), C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_int), C.c_void_p], C.c_int),
+        "pph_transient_steps_record_device": ([p, C.POINTER(SolverCfg), C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                               C.POINTER(C.c_int), C.c_void_p], C.c_int),
+        "pph_transient_bilinear": ([p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, f64p], C.c_int),
+        "pph_transient_bilinear_device": ([p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, f64p], C.c_int),
+        "pph_eval_points_adjoint": ([p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_double, C.c_void_p, i64p], C.c_int),
+        "pph_eval_points_adjoint_device": ([p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_double, C.c_void_p, i64p], C.c_int),
+        "pph_transient_adjoint": ([p, C.POINTER(SolverCfg)] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_double, C.c_int]
+                                  + [C.c_void_p] * 4 + [C.POINTER(C.c_int)], C.c_int),
+        "pph_transient_adjoint_device": ([p, C.POINTER(SolverCfg)] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_double, C.c_int]
+                                         + [C.c_void_p] * 4 + [C.POINTER(C.c_int)], C.c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = ABI mismatch: fail loudly
@@ -748,11 +763,15 @@ class Context:
         self._check(lib.pph_transient_begin(self._h, float(k1), float(k2), float(beta), float(mu), S1, S2, float(theta),
                                             float(dt), int(monolithic)))
 
-    def transient_steps(self, cfg: SolverCfg, p, nsteps: int, steady_tol: float = 0.0, raise_on_diverged: bool = True):
+    def transient_steps(self, cfg: SolverCfg, p, nsteps: int, steady_tol: float = 0.0, raise_on_diverged: bool = True,
+                        record: bool = False):
         """Advances the mixed field p (2n values, field-major) by up to `nsteps` theta steps IN PLACE: a float64 NumPy array
         (copied in and out) or a device tensor (pph_transient_steps / pph_transient_steps_device).  Returns (steps_done,
-        infos [steps_done] of SolveInfo, norms [steps_done, 2] = (||b_s||, ||d_s||))."""
+        infos [steps_done] of SolveInfo, norms [steps_done, 2] = (||b_s||, ||d_s||)); with ``record`` a fourth entry, the
+        trajectory [steps_done + 1, 2n] of the same kind as p (pph_transient_steps_record*)."""
         nsteps = int(nsteps)
+        if record:
+            return self._transient_steps_record(cfg, p, nsteps, steady_tol, raise_on_diverged)
         infos = (SolveInfo * max(nsteps, 1))()
         norms = np.zeros((max(nsteps, 1), 2), dtype=np.float64)
         done = C.c_int(0)
@@ -772,6 +791,127 @@ class Context:
         self.last_info = infos[k - 1] if k > 0 else SolveInfo()
         self._check(st, allow_diverged=not raise_on_diverged)
         return k, [infos[i] for i in range(k)], norms[:k].copy()
+
+    def _transient_steps_record(self, cfg: SolverCfg, p, nsteps: int, steady_tol: float, raise_on_diverged: bool):
+        infos = (SolveInfo * max(nsteps, 1))()
+        norms = np.zeros((max(nsteps, 1), 2), dtype=np.float64)
+        done = C.c_int(0)
+        if isinstance(p, np.ndarray):
+            if p.dtype != np.float64 or p.shape != (2 * self.n,) or not p.flags.c_contiguous or not p.flags.writeable:
+                raise ValueError(f"transient_steps: p must be a writeable contiguous float64 array of {2 * self.n} values")
+            traj = np.zeros((max(nsteps, 0) + 1, 2 * self.n), dtype=np.float64)
+            st = lib.pph_transient_steps_record(self._h, C.byref(cfg), _ptr(p), nsteps, float(steady_tol), infos, _ptr(norms),
+                                                C.byref(done), _ptr(traj))
+        else:
+            t = self._device_in(p, 2 * self.n, "mixed field")
+            if t.data_ptr() != p.data_ptr():
+                raise ValueError("transient_steps: p must be a contiguous float64 device tensor (it is advanced in place)")
+            traj = self._device_out((max(nsteps, 0) + 1) * 2 * self.n).reshape(max(nsteps, 0) + 1, 2 * self.n)
+            st = lib.pph_transient_steps_record_device(self._h, C.byref(cfg), _tptr(t), nsteps, float(steady_tol), infos,
+                                                       _ptr(norms), C.byref(done), _tptr(traj))
+            self.torch_waits()
+        k = int(done.value)
+        self.last_info = infos[k - 1] if k > 0 else SolveInfo()
+        self._check(st, allow_diverged=not raise_on_diverged)
+        return k, [infos[i] for i in range(k)], norms[:k].copy(), traj[:k + 1]
+
+    # -- transient adjoint (pph_transient_adjoint.hip) ------------------------------------------------------------------
+    def transient_bilinear(self, w, p0, p1, theta: float) -> tuple:
+        """The five forms of one backward step, (w1^T K pm1, w2^T K pm2, (w1 - w2)^T M (pm1 - pm2), w1^T M d1, w2^T M d2) with
+        pm = p0 + theta (p1 - p0), d = p1 - p0, of three mixed fields (2n values each; all arrays or all device tensors), in
+        one matrix-free pass (pph_transient_bilinear / pph_transient_bilinear_device)."""
+        args = [self._nodal_arg(v, 2 * self.n, name) for v, name in ((w, "adjoint field"), (p0, "state"), (p1, "next state"))]
+        if len({a[2] for a in args}) != 1:
+            raise ValueError("transient_bilinear: the three fields must be arrays or all device tensors")
+        out = (C.c_double * 5)()
+        fn = lib.pph_transient_bilinear_device if args[0][2] else lib.pph_transient_bilinear
+        self._check(fn(self._h, args[0][1], args[1][1], args[2][1], float(theta), out))
+        return tuple(out[i] for i in range(5))
+
+    def eval_points_adjoint(self, points, weights, out=None, ncomp: int = 1, tol: float = 1e-12):
+        """The transpose of eval_points: (out [n * ncomp] with out[node, k] += sum_m phi_node(x_m) weights[m, k], number of
+        points outside).  points [m, dim], weights [m, ncomp]: arrays or device tensors (pph_eval_points_adjoint*); ``out``
+        is added to IN PLACE when given (same kind), else starts from zeros.  Points are taken one after the other: linear
+        in m."""
+        ncomp = int(ncomp)
+        nout = C.c_int64()
+        if isinstance(points, np.ndarray):
+            x = np.ascontiguousarray(points, dtype=np.float64)
+            c = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1, ncomp)
+            if x.ndim != 2 or x.shape[1] != self.dim or c.shape[0] != x.shape[0]:
+                raise ValueError(f"points must be [m, {self.dim}] and weights [m, {ncomp}], got {x.shape}, {c.shape}")
+            if out is None:
+                out = np.zeros(self.n * ncomp, dtype=np.float64)
+            elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.shape == (self.n * ncomp,)
+                      and out.flags.c_contiguous and out.flags.writeable):
+                raise ValueError(f"out must be a writeable contiguous float64 array of {self.n * ncomp} values")
+            self._check(lib.pph_eval_points_adjoint(self._h, _ptr(x), int(x.shape[0]), _ptr(c), ncomp, float(tol), _ptr(out),
+                                                    C.byref(nout)))
+            return out, int(nout.value)
+        import torch
+
+        if not (isinstance(points, torch.Tensor) and points.dtype == torch.float64 and points.is_cuda and points.dim() == 2
+                and points.shape[1] == self.dim and points.is_contiguous() and points.device.index == self.device):
+            raise ValueError(f"points must be a contiguous float64 tensor [m, {self.dim}] on cuda:{self.device}")
+        m = points.shape[0]
+        c = self._device_in(weights.reshape(-1), m * ncomp, "weights")
+        if out is None:
+            out = torch.zeros(self.n * ncomp, dtype=torch.float64, device=self.torch_device())
+        else:
+            o = self._device_in(out, self.n * ncomp, "out")
+            if o.data_ptr() != out.data_ptr():
+                raise ValueError("out must be a contiguous float64 device tensor (it is added to in place)")
+        self.wait_for_torch()
+        self._check(lib.pph_eval_points_adjoint_device(self._h, _tptr(points), int(m), _tptr(c), ncomp, float(tol), _tptr(out),
+                                                       C.byref(nout)))
+        self.torch_waits()
+        return out, int(nout.value)
+
+    def transient_adjoint(self, cfg: SolverCfg, traj, g=None, obs_x=None, obs_c=None, obs_tol: float = 1e-12,
+                          want_wsum: bool = True, raise_on_diverged: bool = True):
+        """The backward loop over a recorded trajectory traj [N + 1, 2n] (pph_transient_adjoint*): g [N + 1, 2n] and / or the
+        observation form obs_x [m, dim], obs_c [N + 1, m, 2]; all arrays or all device tensors.  Returns (terms [N, 5] array,
+        q0, wsum or None, infos [steps_done], steps_done); q0 and wsum are of the kind of traj."""
+        dev = not isinstance(traj, np.ndarray)
+        n2 = 2 * self.n
+        if tuple(traj.shape[1:]) != (n2,) or traj.shape[0] < 2:
+            raise ValueError(f"traj must have shape [N + 1, {n2}] with N >= 1, got {tuple(traj.shape)}")
+        N = int(traj.shape[0]) - 1
+        if g is None and obs_c is None:
+            raise ValueError("transient_adjoint: neither g nor the observation form is given")
+        if (obs_c is None) != (obs_x is None):
+            raise ValueError("transient_adjoint: obs_x and obs_c go together")
+        m = 0 if obs_x is None else int(obs_x.shape[0])
+        if g is not None and tuple(g.shape) != (N + 1, n2):
+            raise ValueError(f"g must have shape [{N + 1}, {n2}], got {tuple(g.shape)}")
+        if obs_c is not None and (tuple(obs_x.shape) != (m, self.dim) or tuple(obs_c.shape) != (N + 1, m, 2)):
+            raise ValueError(f"obs_x must be [m, {self.dim}] and obs_c [{N + 1}, m, 2], got {tuple(obs_x.shape)}, "
+                             f"{tuple(obs_c.shape)}")
+        terms = np.zeros((N, 5), dtype=np.float64)
+        infos = (SolveInfo * N)()
+        done = C.c_int(0)
+        if dev:
+            flat = lambda v, cnt, name: None if v is None else self._device_in(v.reshape(-1), cnt, name)
+            tj, gg = flat(traj, (N + 1) * n2, "traj"), flat(g, (N + 1) * n2, "g")
+            ox, oc = flat(obs_x, m * self.dim, "obs_x"), flat(obs_c, (N + 1) * m * 2, "obs_c")
+            q0 = self._device_out(n2)
+            wsum = self._device_out(n2) if want_wsum else None
+            st = lib.pph_transient_adjoint_device(self._h, C.byref(cfg), _tptr(tj), None if gg is None else _tptr(gg),
+                                                  None if ox is None else _tptr(ox), m, None if oc is None else _tptr(oc),
+                                                  float(obs_tol), N, _ptr(terms), _tptr(q0), None if wsum is None else _tptr(wsum),
+                                                  infos, C.byref(done))
+            self.torch_waits()
+        else:
+            arr = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float64)
+            tj, gg, ox, oc = arr(traj), arr(g), arr(obs_x), arr(obs_c)
+            q0 = np.zeros(n2, dtype=np.float64)
+            wsum = np.zeros(n2, dtype=np.float64) if want_wsum else None
+            st = lib.pph_transient_adjoint(self._h, C.byref(cfg), _ptr(tj), _ptr(gg), _ptr(ox), m, _ptr(oc), float(obs_tol), N,
+                                           _ptr(terms), _ptr(q0), _ptr(wsum), infos, C.byref(done))
+        k = int(done.value)
+        self.last_info = infos[N - k] if k > 0 else SolveInfo()
+        self._check(st, allow_diverged=not raise_on_diverged)
+        return terms, q0, wsum, [infos[s] for s in range(N - k, N)], k
 
     # -- export -------------------------------------------------------------------------------
     def csr(self, which: int):

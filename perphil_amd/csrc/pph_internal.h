@@ -420,6 +420,7 @@ struct pph_ctx {
   // assembly and Dirichlet sets the step operator belongs to
   bool tr_on = false;
   double tr_coef[4] = {0, 0, 0, 0};
+  double tr_theta = 1.0;                // theta of the last pph_transient_begin (the adjoint's pm = p_s + theta d_s)
   double tr_b0 = -1.0;                  // ||b_0|| of the run (the first step after pph_transient_begin; < 0: not taken yet)
   uint64_t tr_asm_epoch = 0;
   int tr_bc_epoch = -1;
@@ -816,6 +817,8 @@ int pph_nodal_flux_launch(pph_ctx* ctx, double k1, double k2, double beta, doubl
 // rhs[f] -= sigma_f F_f M g_f on a degree-1 mesh, matrix-free (pph_transient.hip: the shifted assembly's share of the lifting
 // behind the fused kernels); g1, g2: n values each, rhs: 2n, enqueued on the context stream
 int pph_step_lift(pph_ctx* ctx, double sigma1, double sigma2, const double* g1, const double* g2, double* rhs);
+// b = -F A_unel p (pph_transient.hip: the launch behind pph_dpp_step_rhs_device, not waited for); p, b: 2n values
+int pph_step_rhs_launch(pph_ctx* ctx, double k1, double k2, double beta, double mu, const double* p, double* b);
 // extreme eigenvalues of a symmetric operator by plain Lanczos (pph_eig.hip; out as pph_extreme_eigenvalues documents it)
 int pph_eig_lanczos(pph_ctx* ctx, const Csr& A, double tol, int max_it, int check_every, double* vec_lo, double* vec_hi,
                     double* out);

@@ -262,6 +262,11 @@ static int step_rhs_dev(pph_ctx* ctx, double k1, double k2, double beta, double 
   return step_matfree_launch(ctx, false, p, p + m.n, k1 / mu, beta / mu, k2 / mu, b);
 }
 
+// (for the backward loop of pph_transient_adjoint.hip)
+int pph_step_rhs_launch(pph_ctx* ctx, double k1, double k2, double beta, double mu, const double* p, double* b) {
+  return step_rhs_dev(ctx, k1, k2, beta, mu, p, b);
+}
+
 static int step_check(pph_ctx* ctx, const char* who, double mu, const double* p, const double* b) {
   PPH_REQUIRE(ctx, ctx->mesh_ok, "%s before pph_mesh_build", who);
   PPH_REQUIRE(ctx, ctx->world == 1, "%s is implemented for single-context meshes", who);
@@ -369,6 +374,7 @@ extern "C" int pph_transient_begin(pph_ctx* ctx, double k1, double k2, double be
   PPH_REQUIRE(ctx, theta >= 0.5 && theta <= 1.0, "pph_transient_begin: theta must lie in [1/2, 1], got %g", theta);
   PPH_TRY(pph_assemble_dpp_shifted(ctx, theta * k1, theta * k2, theta * beta, mu, S1 / dt, S2 / dt, monolithic));
   ctx->tr_coef[0] = k1; ctx->tr_coef[1] = k2; ctx->tr_coef[2] = beta; ctx->tr_coef[3] = mu;
+  ctx->tr_theta = theta;
   ctx->tr_asm_epoch = ctx->asm_epoch;
   ctx->tr_bc_epoch = ctx->bc_epoch;
   ctx->tr_b0 = -1.0;
@@ -376,9 +382,10 @@ extern "C" int pph_transient_begin(pph_ctx* ctx, double k1, double k2, double be
   return PPH_OK;
 }
 
-// the loop between the exchange and the restore; `save`: 3 x 2n doubles, then STEP_MAX_BLOCKS partial sums
+// the loop between the exchange and the restore; `save`: 3 x 2n doubles, then STEP_MAX_BLOCKS partial sums; `traj`: NULL, or
+// [nsteps + 1][2n] on the device: row 0 receives p after k_step_constrain, row s + 1 after the update of step s
 static int transient_run(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p, int nsteps, double steady_tol, pph_solve_info* infos,
-                         double* norms, int* steps_done, double* save) {
+                         double* norms, int* steps_done, double* save, double* traj) {
   const int64_t n = ctx->n, N = 2 * n;
   const int grid = (int)(ceil_div64(N, 256) < STEP_MAX_BLOCKS ? ceil_div64(N, 256) : STEP_MAX_BLOCKS);
   double* part = save + 3 * N;
@@ -389,6 +396,7 @@ static int transient_run(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p, int
                      ctx->g[1].p, n);
   la_set(ctx, ctx->u0.p, 0.0, N);
   la_set(ctx, ctx->scal.p + 1, 0.0, 1);
+  if (traj) la_copy(ctx, traj, p, N);
   PPH_HIP(ctx, hipGetLastError());
   int s = 0;
   for (; s < nsteps; ++s) {
@@ -413,6 +421,7 @@ static int transient_run(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p, int
     if (st == PPH_ERR_DIVERGED) { *steps_done = s; return st; }   // (p holds the last completed step)
     hipLaunchKernelGGL(k_step_update, dim3(grid), dim3(256), 0, ctx->stream, p, ctx->sol.p, ctx->bcmask[0].p, ctx->bcmask[1].p, n, part);
     hipLaunchKernelGGL(k_step_sum, dim3(1), dim3(256), 0, ctx->stream, part, grid, ctx->scal.p + 1);
+    if (traj) la_copy(ctx, traj + (int64_t)(s + 1) * N, p, N);
     PPH_HIP(ctx, hipGetLastError());
   }
   *steps_done = s;
@@ -423,9 +432,8 @@ static int transient_run(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p, int
   return PPH_OK;
 }
 
-extern "C" int pph_transient_steps_device(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_dev, int nsteps, double steady_tol,
-                                          pph_solve_info* infos, double* norms, int* steps_done) {
-  if (!ctx) return PPH_ERR_INVALID;
+static int transient_steps_dev(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_dev, int nsteps, double steady_tol,
+                               pph_solve_info* infos, double* norms, int* steps_done, double* traj) {
   if (steps_done) *steps_done = 0;
   PPH_REQUIRE(ctx, ctx->world == 1, "pph_transient_steps is implemented for single-context meshes");
   PPH_REQUIRE(ctx, ctx->tr_on, "pph_transient_steps before pph_transient_begin");
@@ -439,7 +447,7 @@ extern "C" int pph_transient_steps_device(pph_ctx* ctx, const pph_solver_cfg* cf
   const int64_t N = 2 * ctx->n;
   DevBuf<double> save;
   PPH_TRY(save.alloc(ctx, (size_t)(3 * N + STEP_MAX_BLOCKS)));
-  int st = transient_run(ctx, cfg, p_dev, nsteps, steady_tol, infos, norms, steps_done, save.p);
+  int st = transient_run(ctx, cfg, p_dev, nsteps, steady_tol, infos, norms, steps_done, save.p, traj);
   const std::string msg = ctx->err;   // (the solve's message survives the clean-up)
   // the context's right-hand side, lifting and solution again hold the bits they held before the call
   la_copy(ctx, ctx->rhs.p, save.p, N);
@@ -456,22 +464,44 @@ extern "C" int pph_transient_steps_device(pph_ctx* ctx, const pph_solver_cfg* cf
   return st;
 }
 
-extern "C" int pph_transient_steps(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_host, int nsteps, double steady_tol,
-                                   pph_solve_info* infos, double* norms, int* steps_done) {
+extern "C" int pph_transient_steps_device(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_dev, int nsteps, double steady_tol,
+                                          pph_solve_info* infos, double* norms, int* steps_done) {
   if (!ctx) return PPH_ERR_INVALID;
+  return transient_steps_dev(ctx, cfg, p_dev, nsteps, steady_tol, infos, norms, steps_done, nullptr);
+}
+
+extern "C" int pph_transient_steps_record_device(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_dev, int nsteps,
+                                                 double steady_tol, pph_solve_info* infos, double* norms, int* steps_done,
+                                                 double* traj_dev) {
+  if (!ctx) return PPH_ERR_INVALID;
+  if (steps_done) *steps_done = 0;
+  PPH_REQUIRE(ctx, traj_dev != nullptr, "pph_transient_steps_record: NULL buffer");
+  return transient_steps_dev(ctx, cfg, p_dev, nsteps, steady_tol, infos, norms, steps_done, traj_dev);
+}
+
+// the host variants: p (and the trajectory) live on the device for the call
+static int transient_steps_host(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_host, int nsteps, double steady_tol,
+                                pph_solve_info* infos, double* norms, int* steps_done, double* traj_host, bool record) {
   if (steps_done) *steps_done = 0;
   PPH_REQUIRE(ctx, ctx->world == 1, "pph_transient_steps is implemented for single-context meshes");
   PPH_REQUIRE(ctx, ctx->tr_on, "pph_transient_steps before pph_transient_begin");
-  PPH_REQUIRE(ctx, p_host != nullptr && steps_done != nullptr && cfg != nullptr, "pph_transient_steps: NULL buffer");
+  PPH_REQUIRE(ctx, p_host != nullptr && steps_done != nullptr && cfg != nullptr && (!record || traj_host != nullptr),
+              "pph_transient_steps: NULL buffer");
+  PPH_REQUIRE(ctx, nsteps >= 1, "pph_transient_steps: nsteps must be >= 1, got %d", nsteps);
   PPH_HIP(ctx, hipSetDevice(ctx->device));
   const size_t N = 2 * (size_t)ctx->n;
-  DevBuf<double> p;
-  PPH_TRY(p.alloc(ctx, N));
+  DevBuf<double> p;   // p, then the trajectory
+  PPH_TRY(p.alloc(ctx, record ? N * ((size_t)nsteps + 2) : N));
+  double* traj = record ? p.p + N : nullptr;
   int st = PPH_OK;
   hipError_t e = hipMemcpyAsync(p.p, p_host, sizeof(double) * N, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
-    st = pph_transient_steps_device(ctx, cfg, p.p, nsteps, steady_tol, infos, norms, steps_done);
-    if (st >= 0 || st == PPH_ERR_DIVERGED) e = hipMemcpyAsync(p_host, p.p, sizeof(double) * N, hipMemcpyDeviceToHost, ctx->stream);
+    st = transient_steps_dev(ctx, cfg, p.p, nsteps, steady_tol, infos, norms, steps_done, traj);
+    if (st >= 0 || st == PPH_ERR_DIVERGED) {
+      e = hipMemcpyAsync(p_host, p.p, sizeof(double) * N, hipMemcpyDeviceToHost, ctx->stream);
+      if (e == hipSuccess && record)
+        e = hipMemcpyAsync(traj_host, traj, sizeof(double) * N * ((size_t)*steps_done + 1), hipMemcpyDeviceToHost, ctx->stream);
+    }
   }
   const hipError_t es = hipStreamSynchronize(ctx->stream);
   if (e == hipSuccess) e = es;
@@ -481,4 +511,16 @@ extern "C" int pph_transient_steps(pph_ctx* ctx, const pph_solver_cfg* cfg, doub
     return PPH_ERR_HIP;
   }
   return st;
+}
+
+extern "C" int pph_transient_steps(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_host, int nsteps, double steady_tol,
+                                   pph_solve_info* infos, double* norms, int* steps_done) {
+  if (!ctx) return PPH_ERR_INVALID;
+  return transient_steps_host(ctx, cfg, p_host, nsteps, steady_tol, infos, norms, steps_done, nullptr, false);
+}
+
+extern "C" int pph_transient_steps_record(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_host, int nsteps, double steady_tol,
+                                          pph_solve_info* infos, double* norms, int* steps_done, double* traj_host) {
+  if (!ctx) return PPH_ERR_INVALID;
+  return transient_steps_host(ctx, cfg, p_host, nsteps, steady_tol, infos, norms, steps_done, traj_host, true);
 }

@@ -718,6 +718,55 @@ def _outside_unit_box_device(x, boxes: Sequence[int], tol: float):
     return ~torch.all((xi >= -tol) & (xi <= 1.0 + tol), dim=1)
 
 
+def point_sources(V, points, weights, tolerance: Optional[float] = None):
+    """The adjoint of ``Function.at`` on the scalar or vector space ``V``: the nodal values ``b`` with
+    ``b[node] = sum_m phi_node(x_m) weights[m]``, so that ``<weights, u.at(points)> = <b, u>`` for every ``u`` in ``V``
+    (``pph_eval_points_adjoint``).  ``points``: ``[m, dim]``; ``weights``: ``[m]`` (``[m, ncomp]`` on a vector space).  Arrays
+    give an array, CUDA tensors a tensor on the device.  Points are located by the rules of ``at``; one outside the unit
+    square / cube by more than ``tolerance`` raises ``PointNotInDomainError``.  The points are taken one after the other
+    (bitwise reproducible, any number per cell): the cost is linear in ``m`` - wells, not fields of points."""
+    if isinstance(V, MixedFunctionSpace):
+        raise ValueError("point_sources works on one scalar or vector space: use W.sub(f)")
+    mesh = V.mesh()
+    if mesh.distributed:
+        raise NotImplementedError("point_sources is implemented for single-context meshes: build the mesh with comm=COMM_SELF")
+    dim = mesh.dim
+    tol = 1e-12 if tolerance is None else float(tolerance)
+    if not 0.0 <= tol < 0.5:
+        raise ValueError("tolerance must be in [0, 0.5) box-local units")
+    ncomp = V.value_size if isinstance(V, VectorFunctionSpace) else 1
+    dev = _is_tensor(points) and points.is_cuda
+    if dev != (_is_tensor(weights) and weights.is_cuda):
+        raise ValueError("points and weights must both be arrays or both be device tensors")
+    if not dev:
+        points = np.ascontiguousarray(points.detach().numpy() if _is_tensor(points) else points, dtype=np.float64)
+        weights = np.ascontiguousarray(weights.detach().numpy() if _is_tensor(weights) else weights, dtype=np.float64)
+    if len(points.shape) != 2 or points.shape[1] != dim:
+        raise ValueError(f"points must have shape [m, {dim}], got {tuple(points.shape)}")
+    m = int(points.shape[0])
+    if tuple(weights.shape) not in ({(m,), (m, 1)} if ncomp == 1 else {(m, ncomp)}):
+        raise ValueError(f"weights must have shape [{m}{', ' + str(ncomp) if ncomp > 1 else ''}], got {tuple(weights.shape)}")
+    boxes = (mesh.nx, mesh.ny, mesh.nz)[:dim]
+    if not dev:
+        outside = _outside_unit_box(points, boxes, tol)
+        if outside.any():
+            k = int(np.argmax(outside))
+            raise PointNotInDomainError(f"point {tuple(float(c) for c in points[k])} (index {k}) is outside the unit "
+                                        f"{'square' if dim == 2 else 'cube'} by more than the tolerance {tol:g}")
+    deg = getattr(V, "degree", 1)
+    ctx = mesh.context() if deg == 1 else mesh.context(degree=deg)
+    if dev:
+        points, weights = points.detach().contiguous(), weights.detach().contiguous()
+    out, nout = ctx.eval_points_adjoint(points, weights, None, ncomp, tol)
+    if nout:
+        import torch
+
+        k = int(torch.nonzero(_outside_unit_box_device(points, boxes, tol))[0])
+        raise PointNotInDomainError(f"point {tuple(points[k].tolist())} (index {k}) is outside the unit "
+                                    f"{'square' if dim == 2 else 'cube'} by more than the tolerance {tol:g}")
+    return out
+
+
 Expr = Union[float, Constant, np.ndarray, Callable[[np.ndarray], np.ndarray], Function]
 
 

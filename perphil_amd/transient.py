@@ -19,7 +19,7 @@ comes before the first use of a context: a refusal never touches a GPU.
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional, Sequence
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import attr
 import numpy as np
@@ -36,7 +36,9 @@ class TransientSolution:
     ``increment_norms``: per step, the solve's iteration count, ``||b_s||_2`` and ``||d_s||_2``.  ``observations``:
     ``[steps_done + 1, points, 2]`` values of (p1, p2) at ``observe_at`` after every step, step 0 (the initial field with the
     Dirichlet values applied) included, or None.  ``snapshots``: ``{step: Function}`` every ``record_every`` steps (step 0
-    and the last step included), empty when ``record_every`` is 0.  ``info``: what ran."""
+    and the last step included), empty when ``record_every`` is 0.  ``info``: what ran.  ``trajectory``: None, or with
+    ``record_trajectory`` every state ``[steps_done + 1, 2n]`` (a device tensor when torch shares the library's runtime, else
+    an array): what ``transient_sensitivities`` runs backwards over."""
     times: np.ndarray
     solution: fd.Function = attr.field(eq=False)
     iterations: np.ndarray
@@ -45,6 +47,7 @@ class TransientSolution:
     observations: Optional[np.ndarray]
     snapshots: Dict[int, fd.Function] = attr.field(factory=dict, eq=False)
     info: dict = attr.field(factory=dict, eq=False)
+    trajectory: Any = attr.field(default=None, eq=False)
 
     @property
     def steps_done(self) -> int:
@@ -84,12 +87,15 @@ def _initial_values(W, initial, degree: int):
 def solve_dpp_transient(W, model_params: DPPParameters, bcs: List[fd.DirichletBC], initial, dt: float, num_steps: int,
                         storage: Sequence[float] = (1.0, 1.0), theta: float = 1.0, solver_parameters: Dict = {},
                         observe_at=None, record_every: int = 0, steady_tol: float = 0.0,
-                        on_device: bool = False) -> TransientSolution:
+                        on_device: bool = False, record_trajectory: bool = False,
+                        max_trajectory_bytes: int = 8 << 30) -> TransientSolution:
     """Theta time stepping of the transient DPP model from ``initial`` over ``num_steps`` steps of ``dt`` (see the module
     docstring).  ``solver_parameters`` as for ``solve_dpp`` (a dictionary with ``snes_type`` other than ``ksponly`` as for
     ``solve_dpp_nonlinear``: the Picard presets); ``DPPParameters`` keeps the reference's fields, the storage coefficients
     stand beside it.  ``steady_tol > 0`` stops before the step whose right-hand side has ``||b_s|| <= steady_tol ||b_0||``.
-    ``on_device``: the returned Functions stay on the device (needs torch on the library's HIP runtime)."""
+    ``on_device``: the returned Functions stay on the device (needs torch on the library's HIP runtime).
+    ``record_trajectory``: keep every state in ``TransientSolution.trajectory`` (``(num_steps + 1) 2n`` doubles, refused above
+    ``max_trajectory_bytes`` and together with ``steady_tol > 0``; there is no checkpointing)."""
     degree = _mixed_space(W)
     mesh = W.mesh()
     if mesh.distributed:
@@ -116,6 +122,14 @@ def solve_dpp_transient(W, model_params: DPPParameters, bcs: List[fd.DirichletBC
         raise ValueError(f"record_every must be >= 0, got {record_every}")
     if math.isnan(steady_tol):
         raise ValueError("steady_tol must be a number")
+    if record_trajectory:
+        if steady_tol > 0.0:
+            raise ValueError("record_trajectory records a run of exactly num_steps steps: it cannot be combined with steady_tol > 0")
+        nbytes = (num_steps + 1) * W.local_dim() * 8
+        if nbytes > int(max_trajectory_bytes):
+            raise ValueError(f"the trajectory of {num_steps + 1} states of {W.local_dim()} values takes {nbytes} bytes "
+                             f"({nbytes / 2 ** 30:.3g} GiB), more than max_trajectory_bytes = {int(max_trajectory_bytes)}; "
+                             "trajectories are not checkpointed")
     p0 = _initial_values(W, initial, degree)
     pts = None
     if observe_at is not None:
@@ -162,6 +176,7 @@ def solve_dpp_transient(W, model_params: DPPParameters, bcs: List[fd.DirichletBC
     done = 0
     first = True
     converged = True
+    traj = None
     while done < num_steps:
         want = min(chunk, num_steps - done)
         if first:
@@ -174,7 +189,17 @@ def solve_dpp_transient(W, model_params: DPPParameters, bcs: List[fd.DirichletBC
                     obs.append(observe())
                 if record_every > 0:
                     snaps[0] = snapshot(0)
-        k, infos, norms = ctx.transient_steps(cfg, p, want, steady_tol=steady_tol, raise_on_diverged=True)
+        if record_trajectory:
+            k, infos, norms, rows = ctx.transient_steps(cfg, p, want, steady_tol=steady_tol, raise_on_diverged=True, record=True)
+            if want == num_steps:
+                traj = rows
+            else:   # (row `done` is written again with the bits it holds)
+                if traj is None:
+                    traj = torch.empty((num_steps + 1, 2 * n), dtype=torch.float64, device=p.device) if shared \
+                        else np.empty((num_steps + 1, 2 * n), dtype=np.float64)
+                traj[done:done + k + 1] = rows
+        else:
+            k, infos, norms = ctx.transient_steps(cfg, p, want, steady_tol=steady_tol, raise_on_diverged=True)
         its += [int(i.iterations) for i in infos]
         converged = converged and all(bool(i.converged) for i in infos)
         bn += [float(v) for v in norms[:, 0]]
@@ -190,7 +215,8 @@ def solve_dpp_transient(W, model_params: DPPParameters, bcs: List[fd.DirichletBC
     info.update(steps_done=done, theta=theta, dt=dt, storage=(S1, S2), converged=converged, timers=ctx.timers())
     return TransientSolution(times=dt * np.arange(done + 1), solution=final, iterations=np.array(its, dtype=np.int64),
                              rhs_norms=np.array(bn), increment_norms=np.array(dn),
-                             observations=None if pts is None else np.stack(obs), snapshots=snaps, info=info)
+                             observations=None if pts is None else np.stack(obs), snapshots=snaps, info=info,
+                             trajectory=None if traj is None else traj[:done + 1])
 
 
 def _constrain(ctx, W, bcs, p, n: int, shared: bool) -> None:
@@ -206,3 +232,218 @@ def _constrain(ctx, W, bcs, p, n: int, shared: bool) -> None:
         else:
             v = vals.cpu().numpy() if fd._is_tensor(vals) else np.asarray(vals, dtype=np.float64)
             p[np.asarray(nodes.cpu().numpy() if fd._is_tensor(nodes) else nodes) + off] = v
+
+
+# -- transient adjoint ---------------------------------------------------------------------------------------------------
+@attr.define(frozen=True)
+class TransientSensitivities:
+    """Gradients of a functional ``J = sum_s j_s(p_s)`` of a transient solve.  ``k1, k2, beta, mu``: dJ/d(parameter) (``mu``
+    sets the time scale: not 0 here).  ``storage``: (dJ/dS1, dJ/dS2).  ``initial``: dJ/d(initial field), a Function on W, 0 on
+    constrained dofs (their initial values are overwritten by the Dirichlet data).  ``bcs``: None, or per field a scalar
+    Function holding dJ/d(boundary value) on the boundary nodes and 0 elsewhere.  ``terms``: ``[N, 5]``, the bilinear forms of
+    every backward step (``pph_transient_adjoint``); the gradients are made of their sums in the order N-1 down to 0.
+    ``info``: the backward solves'."""
+    k1: float
+    k2: float
+    beta: float
+    mu: float
+    storage: Tuple[float, float]
+    initial: fd.Function = attr.field(eq=False)
+    bcs: Optional[Tuple[fd.Function, fd.Function]] = attr.field(default=None, eq=False)
+    terms: np.ndarray = attr.field(default=None, eq=False)
+    info: dict = attr.field(factory=dict, eq=False)
+
+
+def _as_kind(v, device):
+    """`v` (array or tensor) as a contiguous float64 device tensor on `device`, or as a float64 array when `device` is None."""
+    if device is None:
+        return np.ascontiguousarray(v.detach().cpu().numpy() if fd._is_tensor(v) else v, dtype=np.float64)
+    import torch
+
+    t = v.detach() if fd._is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64))
+    return t.to(device=device, dtype=torch.float64).contiguous()
+
+
+def transient_sensitivities(W, model_params: DPPParameters, bcs: List[fd.DirichletBC], solution: TransientSolution, dJ_dp=None,
+                            dJ_dobs=None, observe_at=None, storage: Sequence[float] = (1.0, 1.0), theta: float = 1.0,
+                            dt: float = 1.0, solver_parameters: Dict = {}, adjoint_solver_parameters: Optional[Dict] = None,
+                            wrt_bcs: bool = False) -> TransientSensitivities:
+    """Gradients of ``J = sum_{s=0..N} j_s(p_s)`` over the recorded run ``solution`` (``solve_dpp_transient(...,
+    record_trajectory=True)`` with the same ``model_params, bcs, storage, theta, dt``).  ``dJ_dp``: ``[N + 1, 2n]``, the
+    derivatives dj_s/dp_s; ``dJ_dobs``: ``[N + 1, m, 2]``, the derivatives with respect to the observations (p1, p2) at
+    ``observe_at`` ``[m, dim]`` (turned into nodal loads by the transpose of the point evaluation); at least one of them.
+    One backward sweep with one solve per step on the forward operator (``pph_transient_adjoint``), with
+    ``adjoint_solver_parameters`` or, when None, ``solver_parameters``.  ``wrt_bcs``: also dJ/d(boundary values).  The call
+    assembles the step operator itself: nothing an earlier call left in the context is relied on."""
+    degree = _mixed_space(W)
+    mesh = W.mesh()
+    if mesh.distributed:
+        raise NotImplementedError("transient sensitivities are implemented for single-context meshes: build the mesh with "
+                                  "comm=fd.COMM_SELF")
+    params = solver_parameters if adjoint_solver_parameters is None else adjoint_solver_parameters
+    nonlinear = params.get("snes_type", "ksponly") != "ksponly"
+    cfg, info = solver.translate_options(params, nonlinear=nonlinear)
+    if degree != 1:
+        why = solver.degree2_unsupported(cfg, info)
+        if why is not None:
+            raise NotImplementedError(f"degree-{degree} spaces have no multigrid hierarchy: {why} (use e.g. GMRES + ILU)")
+    S1, S2 = _pair(storage, "storage")
+    if not (S1 > 0 and S2 > 0 and math.isfinite(S1) and math.isfinite(S2)):
+        raise ValueError(f"storage coefficients must be finite and > 0, got {(S1, S2)}")
+    dt, theta = float(dt), float(theta)
+    if not (dt > 0 and math.isfinite(dt)):
+        raise ValueError(f"dt must be finite and > 0, got {dt}")
+    if not 0.5 <= theta <= 1.0:
+        raise ValueError(f"theta must lie in [1/2, 1], got {theta}")
+    traj = getattr(solution, "trajectory", None)
+    n2 = W.local_dim()
+    if traj is None:
+        raise ValueError("solution holds no trajectory: run solve_dpp_transient(..., record_trajectory=True)")
+    if len(traj.shape) != 2 or traj.shape[1] != n2 or traj.shape[0] < 2:
+        raise ValueError(f"solution.trajectory must have shape [N + 1, {n2}] with N >= 1, got {tuple(traj.shape)}")
+    N = int(traj.shape[0]) - 1
+    if dJ_dp is None and dJ_dobs is None:
+        raise ValueError("give dJ_dp, dJ_dobs or both: without either there is no functional to differentiate")
+    if dJ_dp is not None and tuple(dJ_dp.shape) != (N + 1, n2):
+        raise ValueError(f"dJ_dp must have shape [{N + 1}, {n2}], got {tuple(dJ_dp.shape)}")
+    pts = None
+    if dJ_dobs is not None:
+        if observe_at is None:
+            raise ValueError("dJ_dobs needs observe_at, the points the observations were taken at")
+        pts = np.ascontiguousarray(observe_at.detach().cpu().numpy() if fd._is_tensor(observe_at) else observe_at, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] != mesh.dim:
+            raise ValueError(f"observe_at must have shape [m, {mesh.dim}], got {pts.shape}")
+        if tuple(dJ_dobs.shape) != (N + 1, pts.shape[0], 2):
+            raise ValueError(f"dJ_dobs must have shape [{N + 1}, {pts.shape[0]}, 2], got {tuple(dJ_dobs.shape)}")
+        outside = fd._outside_unit_box(pts, (mesh.nx, mesh.ny, mesh.nz)[:mesh.dim], 1e-12)
+        if outside.any():
+            raise fd.PointNotInDomainError(f"observe_at[{int(np.argmax(outside))}] is outside the mesh")
+    k1, k2, beta, mu = (float(getattr(model_params, k)) for k in ("k1", "k2", "beta", "mu"))
+    shared = _ffi.shared_runtime()
+
+    # ---- from here on a context is used ------------------------------------------------------------------------------
+    ctx = mesh.context(degree=degree) if degree != 1 else mesh.context()
+    solver._apply_bcs(ctx, W, bcs)
+    ctx.transient_begin(k1, k2, beta, mu, (S1, S2), theta, dt, monolithic=not cfg.picard)
+    device = ctx.torch_device() if shared else None
+    traj = _as_kind(traj, device)
+    g = None if dJ_dp is None else _as_kind(dJ_dp, device)
+    ox = None if pts is None else _as_kind(pts, device)
+    oc = None if dJ_dobs is None else _as_kind(dJ_dobs, device)
+    terms, q0, wsum, infos, done = ctx.transient_adjoint(cfg, traj, g, ox, oc, want_wsum=wrt_bcs)
+    tot = np.zeros(5)
+    for s in range(N - 1, -1, -1):
+        tot += terms[s]
+    O0, O1, O2, O3, O4 = (float(v) for v in tot)
+    out_bcs = None
+    if wrt_bcs:
+        n = n2 // 2
+        r = ctx.dpp_nodal_flux(wsum, k1, k2, beta, mu)      # A_unel Wsum
+        ctx.set_option("invalidate_KM", 1)                   # (as adjoint.sensitivities: the next assembly is unchanged)
+        gsum = g.sum(0) if g is not None else (r * 0.0)
+        if oc is not None:
+            csum = oc.sum(0)
+            parts = [ctx.eval_points_adjoint(ox, csum[:, f].contiguous() if shared else np.ascontiguousarray(csum[:, f]))[0]
+                     for f in (0, 1)]
+            if shared:
+                import torch
+
+                gsum = gsum + torch.cat(parts)
+            else:
+                gsum = gsum + np.concatenate(parts)
+        fields = []
+        if shared:
+            import torch
+
+            idx = mesh._boundary_index(r.device, degree)[1]
+            for f in (0, 1):
+                t = torch.zeros(n, dtype=torch.float64, device=r.device)
+                t[idx] = gsum[f * n + idx] - r[f * n + idx]
+                fields.append(fd.Function(W.sub(f), t, name=f"dJ_dbc[{f}]"))
+        else:
+            idx = mesh.local_boundary_nodes(degree)
+            for f in (0, 1):
+                t = np.zeros(n, dtype=np.float64)
+                t[idx] = gsum[f * n + idx] - r[f * n + idx]
+                fields.append(fd.Function(W.sub(f), t, name=f"dJ_dbc[{f}]"))
+        out_bcs = tuple(fields)
+    info.update(steps_done=done, iterations=[int(i.iterations) for i in infos], converged=all(bool(i.converged) for i in infos),
+                theta=theta, dt=dt, storage=(S1, S2), timers=ctx.timers())
+    return TransientSensitivities(k1=-O0 / mu, k2=-O1 / mu, beta=-O2 / mu, mu=(k1 * O0 + k2 * O1 + beta * O2) / (mu * mu),
+                                  storage=(-O3 / dt, -O4 / dt), initial=fd.Function(W, q0, name="dJ_dinitial"), bcs=out_bcs,
+                                  terms=terms, info=info)
+
+
+def solve_dpp_transient_torch(W, k1, k2, beta, mu, S1, S2, bcs: List[fd.DirichletBC], initial, dt: float, num_steps: int,
+                              theta: float = 1.0, solver_parameters: Dict = {}, observe_at=None,
+                              adjoint_solver_parameters: Optional[Dict] = None):
+    """``solve_dpp_transient`` as a differentiable torch operation.  Returns the observations ``[num_steps + 1, m, 2]`` at
+    ``observe_at``, or the final 2n state when ``observe_at`` is None, on the mesh's device.  ``k1 .. S2``: float64 0-d
+    tensors (any device) or floats; ``initial``: as for ``solve_dpp_transient`` - when it is a CUDA tensor with
+    ``requires_grad`` it receives dJ/d(initial field).  ``backward`` assembles the step operator of its own parameters again
+    and runs ONE backward sweep (``transient_sensitivities``) with ``adjoint_solver_parameters``, or the forward options when
+    None: a forward solve with other parameters between forward and backward does not change the gradients."""
+    import torch
+
+    from .adjoint import _scalar
+
+    _ffi.require_shared_runtime("solve_dpp_transient_torch")
+    degree = _mixed_space(W)
+    mesh = W.mesh()
+    if mesh.distributed:
+        raise NotImplementedError("transient solves are implemented for single-context meshes: build the mesh with "
+                                  "comm=fd.COMM_SELF")
+    for v in (k1, k2, beta, mu, S1, S2):
+        if fd._is_tensor(v) and (v.dtype != torch.float64 or v.dim() != 0):
+            raise ValueError(f"k1, k2, beta, mu, S1, S2 must be float64 0-d tensors or floats, got {v.dtype} of shape "
+                             f"{tuple(v.shape)}")
+    pts = None
+    if observe_at is not None:
+        pts = np.ascontiguousarray(observe_at.detach().cpu().numpy() if fd._is_tensor(observe_at) else observe_at, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] != mesh.dim:
+            raise ValueError(f"observe_at must have shape [m, {mesh.dim}], got {pts.shape}")
+    track_initial = fd._is_tensor(initial) and initial.is_cuda and initial.requires_grad
+    n = W.sub(0).local_dim()
+    bcs = list(bcs or [])
+
+    class _Transient(torch.autograd.Function):
+        @staticmethod
+        def forward(actx, k1_, k2_, beta_, mu_, S1_, S2_, *init):
+            params = DPPParameters(k1=_scalar(k1_), k2=_scalar(k2_), beta=_scalar(beta_), mu=_scalar(mu_))
+            store = (_scalar(S1_), _scalar(S2_))
+            p0 = init[0].detach() if init else initial
+            sol = solve_dpp_transient(W, params, bcs, p0, dt, num_steps, storage=store, theta=theta,
+                                      solver_parameters=solver_parameters, on_device=True, record_trajectory=True)
+            traj = sol.trajectory
+            actx.pph = (params, store, sol, [(v.device if fd._is_tensor(v) else None) for v in (k1_, k2_, beta_, mu_, S1_, S2_)])
+            if pts is None:
+                return traj[-1].clone()
+            ctx = mesh.context(degree=degree) if degree != 1 else mesh.context()
+            x = torch.from_numpy(pts).to(traj.device)
+            rows = [torch.stack([ctx.eval_points_device(traj[s, f * n:(f + 1) * n].contiguous(), x)[0][:, 0] for f in (0, 1)], dim=1)
+                    for s in range(traj.shape[0])]
+            return torch.stack(rows)
+
+        @staticmethod
+        def backward(actx, grad):
+            params, store, sol, devs = actx.pph
+            traj = sol.trajectory
+            if pts is None:
+                g = torch.zeros_like(traj)
+                g[-1] = grad
+                s = transient_sensitivities(W, params, bcs, sol, dJ_dp=g, storage=store, theta=theta, dt=dt,
+                                            solver_parameters=solver_parameters,
+                                            adjoint_solver_parameters=adjoint_solver_parameters)
+            else:
+                s = transient_sensitivities(W, params, bcs, sol, dJ_dobs=grad.contiguous(), observe_at=pts, storage=store,
+                                            theta=theta, dt=dt, solver_parameters=solver_parameters,
+                                            adjoint_solver_parameters=adjoint_solver_parameters)
+            vals = (s.k1, s.k2, s.beta, s.mu, s.storage[0], s.storage[1])
+            out = [torch.tensor(v, dtype=torch.float64, device=d) if (d is not None and need) else None
+                   for v, d, need in zip(vals, devs, actx.needs_input_grad[:6])]
+            if track_initial:
+                out.append(s.initial.torch() if actx.needs_input_grad[6] else None)
+            return tuple(out)
+
+    extra = [initial] if track_initial else []
+    return _Transient.apply(k1, k2, beta, mu, S1, S2, *extra)
