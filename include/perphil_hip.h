@@ -641,7 +641,9 @@ int pph_comm_times(pph_ctx* ctx, double* out4);
  * behind that assembly's last check kernel, counted when the solve's end retires the dictionary;
  * out[35] product launches of the last solve (or pph_pc_apply) whose smoothing epilogue took its factors 1 / a_ii from a row
  * dictionary's table of inverse diagonals instead of the dinv array (option "sell_dict_dinv"; launches recorded into a
- * captured graph count once, when recorded). */
+ * captured graph count once, when recorded);
+ * out[36] fine-level launches of the last solve (or pph_pc_apply) that swept their vectors descending (option "l3_order";
+ * counted like out[35]). */
 int pph_get_timers(pph_ctx* ctx, double* out, int n);
 /* tuning / profiling switches (no reference counterpart; defaults in brackets):
  *   "op_format" [1]      operator format of the scalar blocks inside block solves / Picard sweeps: 1 stencil-ELL
@@ -719,6 +721,15 @@ int pph_get_timers(pph_ctx* ctx, double* out, int n);
  *                        through the assembly's expression, so the same double - instead of streaming the n-entry array;
  *                        coupling products read the class of the DIAGONAL block's dictionary for that.  A dictionary refused
  *                        on the device, no dictionary, slabs: the array as before.  Takes effect at the next launch
+ *   "l3_order" [1]       (0 or 1, anything else is refused) single context: a fine-level kernel starts its sweep where the
+ *                        kernel before it stopped, so that the vectors both touch are met in the Infinity Cache: the order-free
+ *                        elementwise and transfer kernels run their grid-stride loops descending every other launch, the walk
+ *                        products (k_spmv_dict_walk) take their ranges in reverse.  Kernels with running sums (the CG update, the
+ *                        dot products) stay ascending, the product in front of the update always runs descending, and a cycle's
+ *                        restriction and interpolation share a direction.  Only vectors of at least "l3_order_min_rows"
+ *                        [4 000 000] rows; no item, range or partial-sum slot changes, so results are bit-identical.
+ *                        "l3_walk_order" [1]: 1 the walk's ranges plane-band major (sorted by first plane, then in-plane
+ *                        chunk), 0 in their own order.  0: every launch as without the option.  Takes effect at the next launch
  *   "fold_finals" [1]    single context: the final reductions of p.Ap and of the multigrid cycle's r.z are summed inside the
  *                        kernels that consume them instead of by launches of their own (same sums, same order)
  *   "pmg_fused" [1]      PPH_PC_PMG at degree 2: the smoother steps and residuals of the degree-2 level run in the tile kernels

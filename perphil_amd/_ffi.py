@@ -1136,8 +1136,8 @@ class Context:
         return {"halo_ms": t[0], "allreduce_ms": t[1], "halo_timed": int(t[2]), "allreduce_timed": int(t[3])}
 
     def timers(self) -> dict:
-        t = np.zeros(36, dtype=np.float64)
-        self._check(lib.pph_get_timers(self._h, _ptr(t), 36))
+        t = np.zeros(36 + 1, dtype=np.float64)     # (out[0..35], and out[36] of option l3_order)
+        self._check(lib.pph_get_timers(self._h, _ptr(t), t.size))
         return {"mesh_ms": t[0], "assemble_ms": t[1], "bc_blocks_ms": t[2], "solve_ms": t[3],
                 "spmv_ms": t[4], "spmv_launches": int(t[5]), "spmv_bytes": t[6],
                 "spmv_dot_ms": t[7], "spmv_dot_launches": int(t[8]), "spmv_dot_bytes": t[9],
@@ -1161,4 +1161,7 @@ class Context:
                 "asm_values_stale": int(t[32]), "asm_values_materialized": int(t[33]), "asm_store_repairs": int(t[34]),
                 # product launches of the last solve / preconditioner application whose smoothing epilogue took 1 / a_ii from
                 # a row dictionary's table of inverse diagonals instead of the dinv array (option sell_dict_dinv)
-                "dict_dinv_products": int(t[35])}
+                "dict_dinv_products": int(t[35]),
+                # fine-level launches of the last solve / preconditioner application that swept their vectors descending
+                # (option l3_order; launches recorded into a replayed graph count once, at the capture)
+                "l3_order_descending": int(t[36])}

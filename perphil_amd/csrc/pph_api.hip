@@ -194,6 +194,7 @@ int pph_ctx_destroy(pph_ctx* ctx) {
   ctx->scal.release();
   ctx->pub_ctr.release();
   ctx->onchip_rec.release();
+  ctx->walk_order_tab.release();
   la_release_graphs(ctx);
   if (ctx->h_scal) (void)hipHostFree(ctx->h_scal);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -826,6 +827,20 @@ int pph_set_option(pph_ctx* ctx, const char* name, double value) {
     la_release_graphs(ctx);
     return PPH_OK;
   }
+  if (!strcmp(name, "l3_order")) {   // takes effect at the next launch
+    PPH_REQUIRE(ctx, value == 0.0 || value == 1.0, "l3_order: 0 every kernel sweeps ascending, 1 fine-level kernels alternate their direction (got %g)", value);
+    ctx->l3_order = (int)value;
+    ctx->n_l3_desc = 0; ctx->l3_last = 0;
+    la_release_graphs(ctx);
+    return PPH_OK;
+  }
+  if (!strcmp(name, "l3_order_min_rows")) { ctx->l3_order_min_rows = value > 0.0 ? (int64_t)value : 0; ctx->l3_last = 0; la_release_graphs(ctx); return PPH_OK; }
+  if (!strcmp(name, "l3_walk_order")) {
+    PPH_REQUIRE(ctx, value == 0.0 || value == 1.0, "l3_walk_order: 0 the ranges' own order, 1 plane-band major (got %g)", value);
+    ctx->l3_walk_order = (int)value;
+    la_release_graphs(ctx);
+    return PPH_OK;
+  }
   if (!strcmp(name, "sell_dict_poison")) {
     // tests: mark the dictionaries of the fine blocks as failed ON THE DEVICE only, as a failed re-assembly check would -
     // the products launched for them must then take the stored values (the plain path inside the dictionary kernel)
@@ -958,6 +973,7 @@ int pph_get_timers(pph_ctx* ctx, double* out, int n) {
                         ctx->vals0.stale ? 1.0 : 0.0, (double)ctx->n_values_materialized, (double)ctx->n_store_repairs,
                         (double)ctx->n_dict_dinv};
   for (int i = 0; i < n && i < 36; ++i) out[i] = v[i];
+  if (n > 36) out[36] = (double)ctx->n_l3_desc;   // (option l3_order)
   return PPH_OK;
 }
 

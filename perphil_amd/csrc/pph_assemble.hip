@@ -1427,7 +1427,12 @@ static int blocks_prepare(pph_ctx* ctx, bool want_csr) {
   if (want_csr) { PPH_TRY(pph_ensure_pattern(ctx, ctx->mesh)); PPH_TRY(blocks_alloc_csr(ctx)); }
   PPH_TRY(ctx->rhs.alloc(ctx, (size_t)(2 * n)));
   PPH_TRY(ctx->u0.alloc(ctx, (size_t)(2 * n)));
+  // a fresh solution buffer holds zeros, not what the allocator left there: pph_get_solution before the first solve, and the
+  // loops that save and restore the context's vectors around their own solves, read it (a NaN pattern among recycled bytes
+  // compares unequal to its own copy)
+  const bool sol_fresh = !ctx->sol.p || ctx->sol.n != (size_t)(2 * n);
   PPH_TRY(ctx->sol.alloc(ctx, (size_t)(2 * n)));
+  if (sol_fresh) PPH_HIP(ctx, hipMemsetAsync(ctx->sol.p, 0, sizeof(double) * (size_t)(2 * n), ctx->stream));
   return PPH_OK;
 }
 

@@ -592,6 +592,19 @@ struct pph_ctx {
   int sell_dict_zconst = 1;             // ... without class loads where the classes are constant along z (SellDict::zconst)
   int sell_dict_dinv = 1;               // ... whose smoothing epilogues take 1 / a_ii from the classes' table (SellDict::inv), not from the dinv stream
   int64_t n_dict_dinv = 0;              // product launches that did, since the last solve or preconditioner application began (pph_get_timers out[35])
+  // Sweep direction of the fine-level kernels (option "l3_order"): a kernel that re-reads what the kernel before
+  // it touched last starts where that one stopped, so the tail of the shared vectors is still in the 256 MiB Infinity Cache.
+  // Order-free kernels (elementwise, transfers) run their grid-stride loop descending, the walk products take their ranges
+  // through an order; no item's arithmetic, no range and no partial-sum slot changes - results are those of l3_order 0 bit for bit.
+  int l3_order = 1;                     // 0: every launch ascending (the order before the option existed)
+  int64_t l3_order_min_rows = 4000000;  // ... for vectors of at least this many rows (smaller levels are resident whichever way they are swept)
+  int l3_walk_order = 1;                // order of the walk kernel's ranges: 0 their own (in-plane chunk major), 1 plane-band major
+  int l3_last = 0;                      // direction of the last fine-level launch: 0 ascending, 1 descending
+  int64_t n_l3_desc = 0;                // launches that ran descending, since the last solve or preconditioner application began (pph_get_timers out[36])
+  struct WalkOrder { int64_t P = 0; int planes = 0, grid = 0; };
+  WalkOrder walk_order_key[8];          // plane-band-major range orders built so far (sell_walk_order), one table of PPH_WALK_ORDER_MAX words each
+  int walk_order_next = 0;
+  DevBuf<int32_t> walk_order_tab;
   int sell_dict_walk = 1;               // whole-operator dictionary products of hexahedral blocks: x window in registers (k_spmv_dict_walk)
   int sell_dict_cap = PPH_DICT_CAP;     // classes accepted (tests lower it to force the plain path)
   int sell_rpt = 2, sell_blocks = 0, sell_group = 0;   // SELL SpMV tuning: rows per thread, grid cap, XCD chunk group
@@ -612,6 +625,34 @@ static inline int pph_pick_lanes(const pph_ctx* ctx, int64_t nnz, int64_t nrows)
   if (ctx->spmv_lanes_override > 0) return ctx->spmv_lanes_override;
   const double avg = (double)nnz / (double)(nrows > 0 ? nrows : 1);
   return avg > 40 ? 16 : (avg > 12 ? 8 : 4);
+}
+
+// Option l3_order: the direction (0 ascending, 1 descending) of the next fine-level launch over vectors of `rows` rows.
+// how 0: the opposite of the last fine-level launch's; 1: the same (the one seam of a cycle, between restriction and
+// interpolation - only coarse-level traffic lies between them); 2: descending whatever came before (the product in front of
+// the CG update, which is pinned ascending).  Slabs (world > 1) keep the ascending order: their split products have their own.
+#define PPH_WALK_ORDER_MAX 4096   // ranges of a walk product that can take a tabulated order
+static inline int l3_pick(pph_ctx* ctx, int64_t rows, int how = 0) {
+  if (!ctx->l3_order || ctx->world > 1 || rows < ctx->l3_order_min_rows) return 0;
+  const int d = (how == 2) ? 1 : (how == 1 ? ctx->l3_last : !ctx->l3_last);
+  ctx->l3_last = d;
+  ctx->n_l3_desc += d;
+  return d;
+}
+// The grid-stride loop of an ORDER-FREE kernel in either direction: descending visits the items of the ascending loop, trip
+// after trip and block after block in reverse, with the same thread of a block on the same item modulo 256 (pairs keep their
+// 16-byte alignment) and the same arithmetic per item.  Only for kernels whose items do not depend on each other: a kernel
+// whose threads keep a running sum (k_cg_update_dev, k_mdot, the la_dot kernels) stays ascending - reversing a thread's
+// summation order would change the rounding of its sum.  Do not "complete" the option there.
+#define PPH_DIR_LOOP(i, n, desc)                                                                                          \
+  for (int64_t st_ = (int64_t)gridDim.x * blockDim.x,                                                                      \
+               i = (desc) ? (((int64_t)(n) - 1) / st_) * st_ + (int64_t)(gridDim.x - 1 - blockIdx.x) * blockDim.x + threadIdx.x \
+                          : blockIdx.x * (int64_t)blockDim.x + threadIdx.x;                                                \
+       (desc) ? i >= 0 : i < (int64_t)(n); i += (desc) ? -st_ : st_)                                                       \
+    if (i < (int64_t)(n))
+// a fine-level launch that sweeps ascending whatever the option says (kernels with running sums, kernels outside the option)
+static inline void l3_ascending(pph_ctx* ctx, int64_t rows) {
+  if (rows >= ctx->l3_order_min_rows) ctx->l3_last = 0;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -332,6 +332,7 @@ static int spmv_dispatch(pph_ctx* ctx, const Csr& A, const double* x, const doub
   }
   if (A.val32) {
     // fp32-valued operator (multigrid levels): aligned-wide kernel, 8 lanes per row
+    l3_ascending(ctx, A.nrows);
     const int G = (A.max_row > 0 && A.max_row + 3 <= 16) ? 4 : 8;
     grid = spmv_grid(ctx, A.nrows, 256 / G);
     bytes_per_nnz = 8.0;
@@ -349,6 +350,7 @@ static int spmv_dispatch(pph_ctx* ctx, const Csr& A, const double* x, const doub
   }
   {
     // aligned-wide CSR-vector kernel.  Lanes per row: one 4-wide step covers 4 G entries; rows of up to 29 entries fit G = 8
+    l3_ascending(ctx, A.nrows);
     int G = ctx->spmv_lanes_override > 0 ? ctx->spmv_lanes_override : (A.max_row > 0 && A.max_row + 3 <= 16 ? 4 : 8);
     if (G != 4 && G != 8 && G != 16 && G != 32 && G != 64) G = 8;
     grid = spmv_grid(ctx, A.nrows, 256 / G);
@@ -405,6 +407,7 @@ void la_reset_spmv_stats(pph_ctx* ctx) {
   for (int v = 0; v < 2; ++v) { ctx->t_spmv[v] = 0; ctx->spmv_bytes[v] = 0; ctx->n_spmv[v] = 0; }
   ctx->t_spmv_fine = 0; ctx->spmv_bytes_fine = 0; ctx->n_spmv_fine = 0;
   ctx->n_dict_dinv = 0;
+  ctx->n_l3_desc = 0; ctx->l3_last = 0;   // (option l3_order: a solve starts from the ascending state)
   ctx->t_comm[0] = ctx->t_comm[1] = 0; ctx->n_comm_timed[0] = ctx->n_comm_timed[1] = 0;
 }
 
@@ -516,8 +519,12 @@ static inline int ew_grid(int64_t n) {
 #define EW_LOOP(i, n) \
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
-__global__ void k_set(double* __restrict__ x, double v, int64_t n) { EW_LOOP(i, n) x[i] = v; }
-__global__ void k_copy(double* __restrict__ d, const double* __restrict__ s, int64_t n) { EW_LOOP(i, n) d[i] = s[i]; }
+// (desc: the order-free kernels of option l3_order sweep in either direction - PPH_DIR_LOOP, pph_internal.h; the kernels with
+// running sums below, k_mdot, the dot kernels and the CG updates, stay ascending on purpose)
+__global__ void k_set(double* __restrict__ x, double v, int64_t n, int desc) { PPH_DIR_LOOP(i, n, desc) x[i] = v; }
+__global__ void k_copy(double* __restrict__ d, const double* __restrict__ s, int64_t n, int desc) {
+  PPH_DIR_LOOP(i, n, desc) d[i] = s[i];
+}
 __global__ void k_axpy(double* __restrict__ y, double a, const double* __restrict__ x, int64_t n) {
   EW_LOOP(i, n) y[i] += a * x[i];
 }
@@ -529,8 +536,8 @@ __global__ void k_pmult(double* __restrict__ z, const double* __restrict__ d, co
                         int64_t n) {
   EW_LOOP(i, n) z[i] = d[i] * r[i];
 }
-__global__ void k_sub(double* __restrict__ z, const double* __restrict__ a, const double* __restrict__ b, int64_t n) {
-  EW_LOOP(i, n) z[i] = a[i] - b[i];
+__global__ void k_sub(double* __restrict__ z, const double* __restrict__ a, const double* __restrict__ b, int64_t n, int desc) {
+  PPH_DIR_LOOP(i, n, desc) z[i] = a[i] - b[i];
 }
 __global__ void k_block2(double* __restrict__ z, const double* __restrict__ binv, const double* __restrict__ r,
                          int64_t n) {
@@ -542,23 +549,27 @@ __global__ void k_block2(double* __restrict__ z, const double* __restrict__ binv
 }
 
 void la_set(pph_ctx* ctx, double* x, double v, int64_t n) {
-  hipLaunchKernelGGL(k_set, dim3(ew_grid(n)), dim3(256), 0, ctx->stream, x, v, n);
+  hipLaunchKernelGGL(k_set, dim3(ew_grid(n)), dim3(256), 0, ctx->stream, x, v, n, l3_pick(ctx, n));
 }
 void la_copy(pph_ctx* ctx, double* dst, const double* src, int64_t n) {
   // (a kernel of our own: the runtime's device-to-device copy leaves 35 - 40 us of idle time around each call -
   // profiles/r04_c_gaps256.txt, "after __amd_rocclr_copyBuffer")
-  if (n > 0) hipLaunchKernelGGL(k_copy, dim3(ew_grid(n)), dim3(256), 0, ctx->stream, dst, src, n);
+  if (n > 0) hipLaunchKernelGGL(k_copy, dim3(ew_grid(n)), dim3(256), 0, ctx->stream, dst, src, n, l3_pick(ctx, n));
 }
 void la_axpy(pph_ctx* ctx, double* y, double alpha, const double* x, int64_t n) {
+  l3_ascending(ctx, n);
   hipLaunchKernelGGL(k_axpy, dim3(ew_grid(n)), dim3(256), 0, ctx->stream, y, alpha, x, n);
 }
 void la_axpby(pph_ctx* ctx, double* y, double alpha, const double* x, double beta, int64_t n) {
+  l3_ascending(ctx, n);
   hipLaunchKernelGGL(k_axpby, dim3(ew_grid(n)), dim3(256), 0, ctx->stream, y, alpha, x, beta, n);
 }
 void la_scale(pph_ctx* ctx, double* y, double alpha, int64_t n) {
+  l3_ascending(ctx, n);
   hipLaunchKernelGGL(k_scale, dim3(ew_grid(n)), dim3(256), 0, ctx->stream, y, alpha, n);
 }
 void la_pointwise_mult(pph_ctx* ctx, double* z, const double* d, const double* r, int64_t n) {
+  l3_ascending(ctx, n);
   hipLaunchKernelGGL(k_pmult, dim3(ew_grid(n)), dim3(256), 0, ctx->stream, z, d, r, n);
 }
 // R += sign * (tnew - told) ; told = tnew   (residual bookkeeping of the Picard sweeps: one pass instead of
@@ -573,13 +584,15 @@ __global__ void k_shift(double* __restrict__ R, double* __restrict__ told, const
 }
 
 void la_shift(pph_ctx* ctx, double* R, double* told, const double* tnew, double sign, int64_t n) {
+  l3_ascending(ctx, n);
   hipLaunchKernelGGL(k_shift, dim3(ew_grid(n)), dim3(256), 0, ctx->stream, R, told, tnew, sign, n);
 }
 
 void la_sub(pph_ctx* ctx, double* z, const double* a, const double* b, int64_t n) {
-  hipLaunchKernelGGL(k_sub, dim3(ew_grid(n)), dim3(256), 0, ctx->stream, z, a, b, n);
+  hipLaunchKernelGGL(k_sub, dim3(ew_grid(n)), dim3(256), 0, ctx->stream, z, a, b, n, l3_pick(ctx, n));
 }
 void la_block2_apply(pph_ctx* ctx, double* z, const double* binv, const double* r, int64_t n) {
+  l3_ascending(ctx, n);
   hipLaunchKernelGGL(k_block2, dim3(ew_grid(n)), dim3(256), 0, ctx->stream, z, binv, r, n);
 }
 
@@ -617,6 +630,7 @@ void la_mdot_seg(pph_ctx* ctx, const double* V, int64_t ld, int k, const double*
   const int64_t n = sg.len1 + sg.len2;
   int grid = ew_grid(n);
   if (grid > RED_BLOCKS) grid = RED_BLOCKS;
+  l3_ascending(ctx, n);   // (running sums: ascending whatever option l3_order says)
   int k0 = 0;
   while (k0 < k) {
     const int rem = k - k0;
@@ -833,6 +847,9 @@ int la_run_graph(pph_ctx* ctx, const GraphKey& key, const std::function<int()>& 
   GraphEntry* hit = nullptr;
   for (auto& g : ctx->graphs)
     if (g.key == key) { hit = &g; break; }
+  // (option l3_order: a body starts from, and leaves, the ascending state - a replay, whose launches the host does not walk
+  // through, equals its capture and leaves the state the capture left)
+  struct L3Fixed { pph_ctx* c; explicit L3Fixed(pph_ctx* cc) : c(cc) { c->l3_last = 0; } ~L3Fixed() { c->l3_last = 0; } } l3_fixed(ctx);
   if (!hit) {
     // capture: the launches of `body` are recorded, not executed
     const unsigned long long seq0 = ctx->pub_seq;
@@ -938,6 +955,7 @@ bool la_cg_update_dev(pph_ctx* ctx, double* x, double* r, const double* p, const
   } else {
     la_flush_final(ctx);
   }
+  l3_ascending(ctx, n);   // (pinned: each thread's r.r is a running sum in ascending order)
   hipLaunchKernelGGL(k_cg_update_dev, dim3(grid), dim3(256), 0, ctx->stream, x, r, p, q, ctx->scal.p + slot_num,
                      ctx->scal.p + slot_den, n, sg, part, z0, dinv0, w0, slot_bad >= 0 ? ctx->scal.p + slot_bad : (double*)nullptr,
                      den_part, den_n, den_out, rot_src, rot_dst);
@@ -955,7 +973,7 @@ bool la_cg_update_dev(pph_ctx* ctx, double* x, double* r, const double* p, const
 // p = z + beta p with beta = *num / *den read on the device
 __global__ __launch_bounds__(256) void k_p_update_dev(double* __restrict__ p, const double* __restrict__ z, const double* __restrict__ num,
                                const double* __restrict__ den, int64_t n, const double* __restrict__ num_part, int num_n,
-                               double* num_out) {
+                               double* num_out, int desc) {
   __shared__ double lds[4];
   const double dn = *den;
   // num_part: the numerator's final reduction (r.z of the cycle's last kernel) was left to this kernel
@@ -967,7 +985,7 @@ __global__ __launch_bounds__(256) void k_p_update_dev(double* __restrict__ p, co
     nm = *num;
   }
   const double beta = (dn > 0.0 || dn < 0.0) ? nm / dn : 0.0;   // (r.z = 0: restart the direction, see k_cg_update_dev)
-  EW_LOOP(i, n) p[i] = z[i] + beta * p[i];
+  PPH_DIR_LOOP(i, n, desc) p[i] = z[i] + beta * p[i];   // (order-free: every block sums the same partials in slot order)
 }
 
 void la_p_update_dev(pph_ctx* ctx, double* p, const double* z, int slot_num, int slot_den, int64_t n) {
@@ -979,7 +997,7 @@ void la_p_update_dev(pph_ctx* ctx, double* p, const double* z, int slot_num, int
     la_flush_final(ctx);
   }
   hipLaunchKernelGGL(k_p_update_dev, dim3(ew_grid(n)), dim3(256), 0, ctx->stream, p, z, ctx->scal.p + slot_num,
-                     ctx->scal.p + slot_den, n, num_part, num_n, num_out);
+                     ctx->scal.p + slot_den, n, num_part, num_n, num_out, l3_pick(ctx, n));
 }
 
 int la_fetch(pph_ctx* ctx, int slot, int count) {

@@ -92,9 +92,10 @@ __global__ void k_mask_from_double(uint8_t* __restrict__ m, const double* __rest
 // (xc != null: also the coarse level's pre-smoothing from a zero guess, x_c = dinv_c .* b_c * wc, in the same pass)
 __global__ void k_restrict(double* __restrict__ bc, const double* __restrict__ rf, TStencil st,
                            const uint8_t* __restrict__ mc, const uint8_t* __restrict__ mf, TGeom g,
-                           double* __restrict__ xc, const double* __restrict__ dinvc, const double* __restrict__ wcp) {
+                           double* __restrict__ xc, const double* __restrict__ dinvc, const double* __restrict__ wcp,
+                           int desc) {   // (desc: option l3_order - the transfers are order-free, PPH_DIR_LOOP in pph_internal.h)
   const int64_t nc = (int64_t)g.pxc * g.pyc * g.pzc;
-  NODE_LOOP(id, nc) {
+  PPH_DIR_LOOP(id, nc, desc) {
     const int I = (int)(id % g.pxc);
     const int64_t t = id / g.pxc;
     const int J = (int)(t % g.pyc), K = (int)(t / g.pyc) + g.gzc;
@@ -144,9 +145,10 @@ template <int DIM>
 __global__ __launch_bounds__(256) void k_restrict_q1(double* __restrict__ bc, const double* __restrict__ rf,
                                                      const uint8_t* __restrict__ mc, const uint8_t* __restrict__ mf,
                                                      TGeom g, double* __restrict__ xc, const double* __restrict__ dinvc,
-                                                     const double* __restrict__ wcp, const uint8_t* __restrict__ fast) {
+                                                     const double* __restrict__ wcp, const uint8_t* __restrict__ fast,
+                                                     int desc) {
   const int64_t nc = (int64_t)g.pxc * g.pyc * g.pzc;
-  NODE_LOOP(id, nc) {
+  PPH_DIR_LOOP(id, nc, desc) {
     int I, J, K;
     if (nc < (int64_t)1 << 31) {   // (32-bit index arithmetic where the level allows it)
       const uint32_t i32 = (uint32_t)id, t32 = i32 / (uint32_t)g.pxc, k32 = t32 / (uint32_t)g.pyc;
@@ -223,9 +225,9 @@ __global__ __launch_bounds__(256) void k_restrict_q1(double* __restrict__ bc, co
 template <int TK>
 __global__ __launch_bounds__(256) void k_prolong_to(double* __restrict__ xout, const double* __restrict__ xf,
                                                     const double* __restrict__ xc, const uint8_t* __restrict__ mf,
-                                                    TGeom g) {
+                                                    TGeom g, int desc) {
   const int64_t nf = (int64_t)g.pxf * g.pyf * g.pzf;
-  NODE_LOOP(id, nf) {
+  PPH_DIR_LOOP(id, nf, desc) {
     const double x0 = xf[id];
     // ghost rows (mask bit 2) are interpolated like owned ones: with the ghost planes of xf and xc refreshed, the
     // ghost planes of xout equal the owners' values and the post-smoothing product needs no exchange of its own
@@ -260,10 +262,10 @@ __global__ __launch_bounds__(256) void k_prolong_to(double* __restrict__ xout, c
 // arithmetic of k_prolong_to<0> (an even node's 0.5 (c + c) is c exactly)
 __global__ __launch_bounds__(256) void k_prolong_to_q1(double* __restrict__ xout, const double* __restrict__ xf,
                                                        const double* __restrict__ xc, const uint8_t* __restrict__ mf,
-                                                       TGeom g) {
+                                                       TGeom g, int desc) {
   const int hx = (g.pxf + 1) >> 1;
   const int64_t npairs = (int64_t)hx * g.pyf * g.pzf;
-  NODE_LOOP(pid, npairs) {
+  PPH_DIR_LOOP(pid, npairs, desc) {
     // (32-bit index arithmetic where the level allows it: a 64-bit division is ~100 instructions on this hardware)
     int m, j, kl;
     if (npairs < (int64_t)1 << 31) {
@@ -386,9 +388,9 @@ __global__ __launch_bounds__(256) void k_diag_lam(const int64_t* __restrict__ ro
 // (wp != null: 1 / theta is read from device memory instead of the argument)
 __global__ void k_cheb_init(double* __restrict__ x, double* __restrict__ d, const double* __restrict__ r,
                             const double* __restrict__ dinv, double inv_theta, int zero_guess, int write_d, int64_t n,
-                            const double* __restrict__ wp = nullptr) {
+                            const double* __restrict__ wp = nullptr, int desc = 0) {
   if (wp) inv_theta = *wp;
-  NODE_LOOP(i, n) {
+  PPH_DIR_LOOP(i, n, desc) {
     const double di = dinv[i] * r[i] * inv_theta;
     if (write_d) d[i] = di;  // only the multi-step recurrence needs the direction
     x[i] = zero_guess ? di : x[i] + di;
@@ -469,10 +471,10 @@ int mg_transfer_bench(pph_ctx* ctx, int which, int reps, double* out2) {
       if (i == 5) PPH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
       if (pass == 0)
         hipLaunchKernelGGL(k_prolong_to_q1, dim3(mg_grid((L.n + 1) / 2 + L.py * L.pz)), dim3(256), 0, ctx->stream, L.t.p, L.d.p, C.x.p,
-                           L.maskp[which], tg);
+                           L.maskp[which], tg, 0);
       else
         hipLaunchKernelGGL(k_restrict_q1<3>, dim3(mg_grid(C.n)), dim3(256), 0, ctx->stream, C.b.p, L.r.p, C.maskp[which],
-                           L.maskp[which], tg, C.x.p, C.dinv[which].p, cheb_wp(ctx, 1, which), C.rfast[which].p);
+                           L.maskp[which], tg, C.x.p, C.dinv[which].p, cheb_wp(ctx, 1, which), C.rfast[which].p, 0);
     }
     PPH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     PPH_HIP(ctx, hipEventSynchronize(ctx->ev1));
@@ -778,7 +780,7 @@ static void chebyshev(pph_ctx* ctx, MgLevel& L, int which, const double* b, doub
       r01 = r1;
     }
     hipLaunchKernelGGL(k_cheb_init, dim3(mg_grid(L.n)), dim3(256), 0, ctx->stream, x, L.d.p, r01, L.dinv[which].p, 0.0,
-                       zero_guess ? 1 : 0, 0, L.n, cheb_wp(ctx, (int)(&L - ctx->mg.data()), which));
+                       zero_guess ? 1 : 0, 0, L.n, cheb_wp(ctx, (int)(&L - ctx->mg.data()), which), l3_pick(ctx, L.n));
     return;
   }
   if (mg_lam_host(ctx) != PPH_OK) return;
@@ -798,7 +800,7 @@ static void chebyshev(pph_ctx* ctx, MgLevel& L, int which, const double* b, doub
     la_spmv_resid(ctx, A, x, b, r);
   }
   hipLaunchKernelGGL(k_cheb_init, dim3(grid), dim3(256), 0, ctx->stream, x, L.d.p, r0, L.dinv[which].p, 1.0 / theta,
-                     zero_guess ? 1 : 0, steps > 1 ? 1 : 0, L.n);
+                     zero_guess ? 1 : 0, steps > 1 ? 1 : 0, L.n, (const double*)nullptr, l3_pick(ctx, L.n));
   double *dcur = L.d.p, *dnext = L.t.p;   // (tile kernels: the new direction goes to the other buffer)
   for (int s = 1; s < steps; ++s) {
     const double rho_new = 1.0 / (2.0 * sigma - rho);
@@ -807,6 +809,7 @@ static void chebyshev(pph_ctx* ctx, MgLevel& L, int which, const double* b, doub
       double* sw = dcur; dcur = dnext; dnext = sw;
     } else {
       la_spmv(ctx, A, L.d.p, L.t.p);
+      l3_ascending(ctx, L.n);
       hipLaunchKernelGGL(k_cheb_step, dim3(grid), dim3(256), 0, ctx->stream, x, L.d.p, r, L.t.p, L.dinv[which].p,
                          rho_new * rho, 2.0 * rho_new / delta, L.n);
     }
@@ -1438,7 +1441,7 @@ static void mg_vcycle_fused(pph_ctx* ctx, int which, const double* rin, double* 
     ctx->comm_suspended = L.replicated;
     if (l == 0 && !x0_ready)   // coarser levels: done by the restriction that produced their right-hand side
       hipLaunchKernelGGL(k_cheb_init, dim3(mg_grid(L.n)), dim3(256), 0, ctx->stream, x, L.d.p, b, L.dinv[which].p, 0.0,
-                         1, 0, L.n, cheb_wp(ctx, l, which));
+                         1, 0, L.n, cheb_wp(ctx, l, which), l3_pick(ctx, L.n));
     la_spmv_resid(ctx, level_csr(ctx, L, which), x, b, L.r.p);
     if (dist && !L.replicated) (void)la_halo(ctx, *L.geom, L.r.p);
     // the coarse level's pre-smoothing rides along unless the tail kernel (or the coarsest solve) does it itself
@@ -1448,20 +1451,21 @@ static void mg_vcycle_fused(pph_ctx* ctx, int which, const double* rin, double* 
     const double* wc = init_c ? cheb_wp(ctx, l + 1, which) : nullptr;
     const bool sum_c = dist && C.replicated && !L.replicated;   // partial right-hand sides are summed first
     if (sum_c) { xc = nullptr; }
+    const int rdesc = l3_pick(ctx, L.n);   // (the fine vector L.r decides: the coarse ones are an eighth of it)
     if (kind == PPH_CELL_HEX)
       hipLaunchKernelGGL(k_restrict_q1<3>, dim3(mg_grid(C.n)), dim3(256), 0, ctx->stream, C.b.p, L.r.p, C.maskp[which],
-                         L.maskp[which], tgeom(L, C), xc, dc, wc, C.rfast[which].p);
+                         L.maskp[which], tgeom(L, C), xc, dc, wc, C.rfast[which].p, rdesc);
     else if (kind == PPH_CELL_QUAD)
       hipLaunchKernelGGL(k_restrict_q1<2>, dim3(mg_grid(C.n)), dim3(256), 0, ctx->stream, C.b.p, L.r.p, C.maskp[which],
-                         L.maskp[which], tgeom(L, C), xc, dc, wc, C.rfast[which].p);
+                         L.maskp[which], tgeom(L, C), xc, dc, wc, C.rfast[which].p, rdesc);
     else
       hipLaunchKernelGGL(k_restrict, dim3(mg_grid(C.n)), dim3(256), 0, ctx->stream, C.b.p, L.r.p, st, C.maskp[which],
-                         L.maskp[which], tgeom(L, C), xc, dc, wc);
+                         L.maskp[which], tgeom(L, C), xc, dc, wc, rdesc);
     if (sum_c) {
       (void)la_allreduce_vec(ctx, C.b.p, C.n);
       if (init_c)
         hipLaunchKernelGGL(k_cheb_init, dim3(mg_grid(C.n)), dim3(256), 0, ctx->stream, C.x.p, C.d.p, C.b.p,
-                           C.dinv[which].p, 0.0, 1, 0, C.n, cheb_wp(ctx, l + 1, which));
+                           C.dinv[which].p, 0.0, 1, 0, C.n, cheb_wp(ctx, l + 1, which), l3_pick(ctx, C.n));
     }
   }
   if (lt < nlev) {
@@ -1518,6 +1522,7 @@ static void mg_vcycle_fused(pph_ctx* ctx, int which, const double* rin, double* 
       pph_cg_jacobi(ctx, level_csr(ctx, C, which), C.b.p, C.x.p, C.dinv[which].p, 1e-12, 0.0, ctx->coarse_max_it, C.r.p, C.d.p, C.t.p,
                     C.w.p, &its);
   }
+  bool seam = true;
   for (int l = top - 1; l >= 0; --l) {
     MgLevel& L = mg[l];
     MgLevel& C = mg[l + 1];
@@ -1526,12 +1531,17 @@ static void mg_vcycle_fused(pph_ctx* ctx, int which, const double* rin, double* 
     ctx->comm_suspended = L.replicated;
     if (dist && !C.replicated) (void)la_halo(ctx, *C.geom, C.x.p);
     const TGeom tg = tgeom(L, C);
+    // option l3_order: the first interpolation onto a level the option covers keeps the direction of the last restriction
+    // there - the one seam of the cycle; between the two lies nothing but coarse-level traffic, so there is nothing to reuse.
+    // A one-iteration block solve makes an odd number of fine-level launches around the pinned update: one pair has to agree.
+    const int pdesc = l3_pick(ctx, L.n, seam ? 1 : 0);
+    if (L.n >= ctx->l3_order_min_rows) seam = false;
     if (kind == PPH_CELL_QUAD || kind == PPH_CELL_HEX)
-      hipLaunchKernelGGL(k_prolong_to_q1, dim3(mg_grid((L.n + 1) / 2 + L.py * L.pz)), dim3(256), 0, ctx->stream, L.t.p, x, C.x.p, L.maskp[which], tg);
+      hipLaunchKernelGGL(k_prolong_to_q1, dim3(mg_grid((L.n + 1) / 2 + L.py * L.pz)), dim3(256), 0, ctx->stream, L.t.p, x, C.x.p, L.maskp[which], tg, pdesc);
     else if (kind == PPH_CELL_TET)
-      hipLaunchKernelGGL(k_prolong_to<1>, dim3(mg_grid(L.n)), dim3(256), 0, ctx->stream, L.t.p, x, C.x.p, L.maskp[which], tg);
+      hipLaunchKernelGGL(k_prolong_to<1>, dim3(mg_grid(L.n)), dim3(256), 0, ctx->stream, L.t.p, x, C.x.p, L.maskp[which], tg, pdesc);
     else
-      hipLaunchKernelGGL(k_prolong_to<2>, dim3(mg_grid(L.n)), dim3(256), 0, ctx->stream, L.t.p, x, C.x.p, L.maskp[which], tg);
+      hipLaunchKernelGGL(k_prolong_to<2>, dim3(mg_grid(L.n)), dim3(256), 0, ctx->stream, L.t.p, x, C.x.p, L.maskp[which], tg, pdesc);
     // ghost planes of L.t: x's were refreshed by the residual product of the downward leg, the coarse correction's
     // just above, and k_prolong_to interpolates ghost rows as well - one exchange per level and cycle less
     // (L.dinv is 1 / a_ii of this level's own operator: with a usable row dictionary the product takes it from the classes)
@@ -1594,17 +1604,18 @@ void mg_vcycle(pph_ctx* ctx, int which, const double* rin, double* zout, int nsm
     la_spmv_resid(ctx, level_csr(ctx, L, which, true), x, b, L.r.p);
     if (l == 0 && timed) (void)hipEventRecord(ctx->pmg_ev[1], ctx->stream);
     if (dist && !L.replicated) (void)la_halo(ctx, *L.geom, L.r.p);  // restriction reads one fine plane beyond the owned ones
+    const int rdesc = l3_pick(ctx, L.n);
     if (ctx->mesh.kind == PPH_CELL_HEX)
       hipLaunchKernelGGL(k_restrict_q1<3>, dim3(mg_grid(C.n)), dim3(256), 0, ctx->stream, C.b.p, L.r.p, C.maskp[which],
                          L.maskp[which], tgeom(L, C), (double*)nullptr, (const double*)nullptr, (const double*)nullptr,
-                         C.rfast[which].p);
+                         C.rfast[which].p, rdesc);
     else if (ctx->mesh.kind == PPH_CELL_QUAD)
       hipLaunchKernelGGL(k_restrict_q1<2>, dim3(mg_grid(C.n)), dim3(256), 0, ctx->stream, C.b.p, L.r.p, C.maskp[which],
                          L.maskp[which], tgeom(L, C), (double*)nullptr, (const double*)nullptr, (const double*)nullptr,
-                         C.rfast[which].p);
+                         C.rfast[which].p, rdesc);
     else
       hipLaunchKernelGGL(k_restrict, dim3(mg_grid(C.n)), dim3(256), 0, ctx->stream, C.b.p, L.r.p, st, C.maskp[which],
-                         L.maskp[which], tgeom(L, C), (double*)nullptr, (const double*)nullptr, (const double*)nullptr);
+                         L.maskp[which], tgeom(L, C), (double*)nullptr, (const double*)nullptr, (const double*)nullptr, rdesc);
     if (dist && C.replicated && !L.replicated) (void)la_allreduce_vec(ctx, C.b.p, C.n);
   }
   // coarsest level: Jacobi-CG to 1e-12 (a handful of unknowns)
@@ -1638,6 +1649,7 @@ void mg_vcycle(pph_ctx* ctx, int which, const double* rin, double* zout, int nsm
     if (dist && !C.replicated) (void)la_halo(ctx, *C.geom, C.x.p);  // interpolation reads the coarse ghost plane
     const TGeom tg = tgeom(L, C);
     const int kind = ctx->mesh.kind;
+    l3_ascending(ctx, L.n);   // (k_prolong_add is not part of option l3_order)
     if (kind == PPH_CELL_QUAD || kind == PPH_CELL_HEX)
       hipLaunchKernelGGL(k_prolong_add<0>, dim3(mg_grid(L.n)), dim3(256), 0, ctx->stream, x, C.x.p, L.maskp[which], tg);
     else if (kind == PPH_CELL_TET)
@@ -1658,16 +1670,17 @@ Csr mg_level_csr(const pph_ctx* ctx, int l, int which) { return level_csr(ctx, c
 void mg_restrict_field(pph_ctx* ctx, int l, int which, const double* rf, double* bc) {
   MgLevel& L = ctx->mg[l];
   MgLevel& C = ctx->mg[l + 1];
+  const int rdesc = l3_pick(ctx, L.n);
   if (ctx->mesh.kind == PPH_CELL_HEX)
     hipLaunchKernelGGL(k_restrict_q1<3>, dim3(mg_grid(C.n)), dim3(256), 0, ctx->stream, bc, rf, C.maskp[which], L.maskp[which],
-                       tgeom(L, C), (double*)nullptr, (const double*)nullptr, (const double*)nullptr, C.rfast[which].p);
+                       tgeom(L, C), (double*)nullptr, (const double*)nullptr, (const double*)nullptr, C.rfast[which].p, rdesc);
   else if (ctx->mesh.kind == PPH_CELL_QUAD)
     hipLaunchKernelGGL(k_restrict_q1<2>, dim3(mg_grid(C.n)), dim3(256), 0, ctx->stream, bc, rf, C.maskp[which], L.maskp[which],
-                       tgeom(L, C), (double*)nullptr, (const double*)nullptr, (const double*)nullptr, C.rfast[which].p);
+                       tgeom(L, C), (double*)nullptr, (const double*)nullptr, (const double*)nullptr, C.rfast[which].p, rdesc);
   else
     hipLaunchKernelGGL(k_restrict, dim3(mg_grid(C.n)), dim3(256), 0, ctx->stream, bc, rf, make_transfer_stencil(ctx->mesh.kind),
                        C.maskp[which], L.maskp[which], tgeom(L, C), (double*)nullptr, (const double*)nullptr,
-                       (const double*)nullptr);
+                       (const double*)nullptr, rdesc);
 }
 
 // xf += P xc from level l + 1 to l, 0 on field `which`'s constrained fine dofs
@@ -1676,6 +1689,7 @@ void mg_prolong_add_field(pph_ctx* ctx, int l, int which, double* xf, const doub
   MgLevel& C = ctx->mg[l + 1];
   const TGeom tg = tgeom(L, C);
   const int kind = ctx->mesh.kind;
+  l3_ascending(ctx, L.n);
   if (kind == PPH_CELL_QUAD || kind == PPH_CELL_HEX)
     hipLaunchKernelGGL(k_prolong_add<0>, dim3(mg_grid(L.n)), dim3(256), 0, ctx->stream, xf, xc, L.maskp[which], tg);
   else if (kind == PPH_CELL_TET)

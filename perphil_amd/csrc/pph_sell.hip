@@ -490,7 +490,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE <= 1 ?
                                                         double* __restrict__ y, double* __restrict__ aux,
                                                         double* __restrict__ z0, int64_t n, int px, int64_t pxy, int planes,
                                                         double* __restrict__ part, int64_t dlo, int64_t dhi, int flags,
-                                                        SellDictArgs da) {
+                                                        SellDictArgs da, const int32_t* __restrict__ order, int rev) {
   extern __shared__ double dtab[];
 #ifdef PPH_DW_STAMPS
   unsigned long long* stp = (g_dw_stamps && threadIdx.x == 0) ? g_dw_stamps + (size_t)blockIdx.x * 64 : nullptr;
@@ -511,8 +511,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE <= 1 ?
   double dotx[2] = {0.0, 0.0};
   const int64_t P = (pxy + 511) / 512;
   const int64_t total = P * planes;
-  int64_t q = total * (int64_t)blockIdx.x / gridDim.x;
-  const int64_t q1 = total * ((int64_t)blockIdx.x + 1) / gridDim.x;
+  // Option l3_order: workgroup b takes range rid = order[b] (null: b), counted from the far end with rev, instead of range b.
+  // The ranges themselves and the slot of a range's partial sum, part[rid], are those of the plain order: every product and
+  // every dot product - the pending final reductions that the update kernels sum in slot order included - keeps its bits.
+  int rid = rev ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;
+  if (order) {
+    const int o = __builtin_amdgcn_readfirstlane(order[rid]);
+    if ((unsigned)o < gridDim.x) rid = o;   // (a table is a permutation of the ranges: sell_walk_order)
+  }
+  int64_t q = total * (int64_t)rid / gridDim.x;
+  const int64_t q1 = total * ((int64_t)rid + 1) / gridDim.x;
   while (q < q1) {
     const int64_t pos = q / planes;
     int z = (int)(q - pos * planes);
@@ -630,7 +638,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE <= 1 ?
     dotacc = sell_wave_sum(dotacc);
     if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = dotacc;
     __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
+    if (threadIdx.x == 0) part[rid] = lds[0] + lds[1] + lds[2] + lds[3];
     if (MODE == 7) {
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
@@ -638,7 +646,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE <= 1 ?
         const double t = sell_wave_sum(dotx[k]);
         if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = t;
         __syncthreads();
-        if (threadIdx.x == 0) part[(int64_t)(k + 1) * PPH_PART_STRIDE + blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
+        if (threadIdx.x == 0) part[(int64_t)(k + 1) * PPH_PART_STRIDE + rid] = lds[0] + lds[1] + lds[2] + lds[3];
       }
     }
   }
@@ -681,6 +689,40 @@ static SellDictArgs sell_dict_args(const SellDict& D, int zconst, int mode, cons
   return da;
 }
 
+// Plane-band-major order of the walk kernel's ranges (option l3_walk_order 1): range r begins at step q0 = total r / G =
+// pos planes + z of the walk (in-plane chunk pos, plane z); tab[k] is the range with the k-th smallest (z, pos).  Workgroups
+// are dispatched in ascending block order, so the product then moves through the planes - through the addresses - as the
+// elementwise and transfer kernels around it do, where the ranges' own order finishes one in-plane chunk after the other.
+__global__ void k_walk_order(int32_t* __restrict__ tab, int64_t total, int planes, int G) {
+  const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (r >= G) return;
+  const int64_t P = total / planes;
+  auto key = [&](int rr) { const int64_t q0 = total * (int64_t)rr / G; return (q0 % planes) * P + q0 / planes; };
+  const int64_t mine = key(r);
+  int rank = 0;
+  for (int o = 0; o < G; ++o) rank += key(o) < mine ? 1 : 0;   // (the ranges are not empty, G <= total: the keys differ)
+  tab[rank] = r;
+}
+
+// the table for (P, planes, grid), built once by a launch on the context's stream and kept; null (the ranges' own order)
+// where none can be had: more ranges than a table holds, or a first use while the stream is being captured into a graph
+static const int32_t* sell_walk_order(pph_ctx* ctx, int64_t P, int planes, int grid) {
+  if (grid > PPH_WALK_ORDER_MAX || grid > P * planes) return nullptr;
+  for (int k = 0; k < 8; ++k) {
+    const pph_ctx::WalkOrder& W = ctx->walk_order_key[k];
+    if (W.grid == grid && W.P == P && W.planes == planes) return ctx->walk_order_tab.p + (size_t)k * PPH_WALK_ORDER_MAX;
+  }
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return nullptr; }
+  if (!ctx->walk_order_tab.p && ctx->walk_order_tab.alloc(ctx, (size_t)8 * PPH_WALK_ORDER_MAX) < 0) return nullptr;
+  const int k = ctx->walk_order_next;
+  ctx->walk_order_next = (k + 1) % 8;
+  int32_t* tab = ctx->walk_order_tab.p + (size_t)k * PPH_WALK_ORDER_MAX;
+  hipLaunchKernelGGL(k_walk_order, dim3((grid + 255) / 256), dim3(256), 0, ctx->stream, tab, P * planes, planes, grid);
+  ctx->walk_order_key[k].P = P; ctx->walk_order_key[k].planes = planes; ctx->walk_order_key[k].grid = grid;
+  return tab;
+}
+
 // launches the walk kernel for a whole-operator product on a usable dictionary; returns the grid, 0 = not applicable
 static int sell_launch_dict_walk(pph_ctx* ctx, int mode, const Sell& E, const double* x, const double* b, const double* dinv,
                                  const double* w, double* y, double* aux, double* z0, int64_t n, double* part, int64_t dlo,
@@ -698,24 +740,29 @@ static int sell_launch_dict_walk(pph_ctx* ctx, int mode, const Sell& E, const do
   if (g * 12 > items) g = items / 12 > ctx->num_cus ? items / 12 : ctx->num_cus;
   if (g > items) g = items;
   const int grid = (int)g;
+  // option l3_order: the product in front of the CG update (modes 2 and 7; the update is pinned ascending) runs descending,
+  // every other one against the launch before it
+  const int rev = l3_pick(ctx, n, (mode == 2 || mode == 7) ? 2 : 0);
+  const int32_t* order = (ctx->l3_order && ctx->l3_walk_order == 1 && n >= ctx->l3_order_min_rows && ctx->world == 1)
+                             ? sell_walk_order(ctx, (pxy + 511) / 512, E.pz, grid) : nullptr;
 #define PPH_DW_GO(MM)                                                                                                       \
   do {                                                                                                                       \
     if (da.zconst)                                                                                                           \
       hipLaunchKernelGGL((k_spmv_dict_walk<MM, true>), dim3(grid), dim3(256), lds, ctx->stream, E.val, E.ld, x, b, dinv, w, y, aux, \
-                         z0, n, E.px, pxy, E.pz, part, dlo, dhi, ctx->sell_flags, da);                                       \
+                         z0, n, E.px, pxy, E.pz, part, dlo, dhi, ctx->sell_flags, da, order, rev);                                       \
     else                                                                                                                     \
       hipLaunchKernelGGL((k_spmv_dict_walk<MM, false>), dim3(grid), dim3(256), lds, ctx->stream, E.val, E.ld, x, b, dinv, w, y, aux, \
-                         z0, n, E.px, pxy, E.pz, part, dlo, dhi, ctx->sell_flags, da);                                       \
+                         z0, n, E.px, pxy, E.pz, part, dlo, dhi, ctx->sell_flags, da, order, rev);                                       \
   } while (0)
 #define PPH_DW_GOT(MM)                                                                                                      \
   do {                                                                                                                       \
     if (!tinv) { PPH_DW_GO(MM); break; }                                                                                     \
     if (da.zconst)                                                                                                           \
       hipLaunchKernelGGL((k_spmv_dict_walk<MM, true, true>), dim3(grid), dim3(256), lds, ctx->stream, E.val, E.ld, x, b, dinv, w, y, \
-                         aux, z0, n, E.px, pxy, E.pz, part, dlo, dhi, ctx->sell_flags, da);                                  \
+                         aux, z0, n, E.px, pxy, E.pz, part, dlo, dhi, ctx->sell_flags, da, order, rev);                                  \
     else                                                                                                                     \
       hipLaunchKernelGGL((k_spmv_dict_walk<MM, false, true>), dim3(grid), dim3(256), lds, ctx->stream, E.val, E.ld, x, b, dinv, w, y, \
-                         aux, z0, n, E.px, pxy, E.pz, part, dlo, dhi, ctx->sell_flags, da);                                  \
+                         aux, z0, n, E.px, pxy, E.pz, part, dlo, dhi, ctx->sell_flags, da, order, rev);                                  \
   } while (0)
   switch (mode) {
     case 0: PPH_DW_GO(0); break;
@@ -839,6 +886,7 @@ int sell_spmv(pph_ctx* ctx, const Sell& E, int64_t n, int mode, const double* x,
     const int g = sell_launch_dict_walk(ctx, mode, E, x, b, dinv, w, y, aux, z0, n, part, dlo, dhi, dd);
     if (g > 0) return g;
   }
+  l3_ascending(ctx, n);   // (the chunk kernels below sweep ascending)
   int cap = (ctx->sell_blocks >= 8 && ctx->sell_blocks <= 8192) ? (ctx->sell_blocks / 8) * 8
                                                                  : (zw ? ((ctx->num_cus + 7) / 8) * 8 : 4096);
   // (a dictionary product streams vectors only: nothing to keep in L2 for a second reader, many waves to hide latency)

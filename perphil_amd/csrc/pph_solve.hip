@@ -728,9 +728,8 @@ struct BlockSolver {
 // the solve entry point
 // ------------------------------------------------------------------------------------------------
 __global__ void k_add2(double* __restrict__ out, const double* __restrict__ a, const double* __restrict__ b,
-                       int64_t n) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = a[i] + b[i];
+                       int64_t n, int desc) {   // (desc: option l3_order, PPH_DIR_LOOP in pph_internal.h)
+  PPH_DIR_LOOP(i, n, desc) out[i] = a[i] + b[i];
 }
 
 int validate_cfg(pph_ctx* ctx, const pph_solver_cfg* cfg) {   // (also pph_solve_rhs*, pph_adjoint.hip)
@@ -1033,7 +1032,7 @@ int pph_solve_device(pph_ctx* ctx, const pph_solver_cfg* cfg, pph_solve_info* in
   // u = u0 + du
   {
     int grid = (int)(ceil_div64(N, 256) < 2048 ? ceil_div64(N, 256) : 2048);
-    hipLaunchKernelGGL(k_add2, dim3(grid), dim3(256), 0, ctx->stream, ctx->sol.p, ctx->u0.p, du, N);
+    hipLaunchKernelGGL(k_add2, dim3(grid), dim3(256), 0, ctx->stream, ctx->sol.p, ctx->u0.p, du, N, l3_pick(ctx, N));
   }
   // the record of the on-chip block solves travels with the solve's last launches (pinned destination: no wait of its own)
   if (bs.onchip_used)
@@ -1216,6 +1215,7 @@ int pph_pc_apply(pph_ctx* ctx, int which, int pc_type, int mg_smooth, const doub
   PPH_REQUIRE(ctx, r_host && z_host, "NULL vector");
   PPH_TRY(pc_apply_prepare(ctx, which, &pc_type));
   ctx->n_dict_dinv = 0;   // (counts this application's launches, as a solve's)
+  ctx->n_l3_desc = 0; ctx->l3_last = 0;
   const int64_t n = ctx->n;
   DevBuf<double> r, z, w;
   PPH_TRY(r.alloc(ctx, (size_t)n));
