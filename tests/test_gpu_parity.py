@@ -297,6 +297,19 @@ def test_picard_fixed_point(gpu_ctx_factory, goldens, inner):
     np.testing.assert_allclose(p1, g["p1"], rtol=3e-4)
 
 
+def test_picard_fixed_point_gmres_blocks(gpu_ctx_factory):
+    """The sweeps of test_picard_fixed_point with restarted GMRES + Jacobi on the blocks: the first sweep solves cold, every
+    later one warm (for the correction, from the block's true residual).  Same assertions and tolerances."""
+    f = _ffi()
+    ctx, om, osys = _setup(gpu_ctx_factory, 2, o.CELL_QUAD, 32, 32, 0, monolithic=False)
+    x, info, hist = ctx.solve(_cfg(picard=1, inner_ksp_type=f.KSP_GMRES, inner_pc_type=f.PC_JACOBI, inner_rtol=1e-12), hist_cap=64)
+    _, its, res, ohist = o.picard(osys)
+    assert info.iterations == its and info.converged and its > 1
+    np.testing.assert_allclose(hist, ohist, rtol=1e-5)
+    ud = o.solve_direct(osys)
+    assert np.abs(x - ud).max() / np.abs(ud).max() < 1e-8
+
+
 @pytest.mark.parametrize("dim,kind,n,k2", [(3, o.CELL_HEX, 16, 1e-2), (3, o.CELL_HEX, 16, 1e-4), (3, o.CELL_TET, 8, 1e-2),
                                            (2, o.CELL_QUAD, 32, 1e-2), (2, o.CELL_TRI, 32, 1e-2)])
 def test_mg_pcg_iterations_match_mg_oracle(gpu_ctx_factory, dim, kind, n, k2):
