@@ -565,6 +565,65 @@ int pph_transient_adjoint(pph_ctx* ctx, const pph_solver_cfg* cfg, const double*
                           const double* obs_x_host, int64_t m, const double* obs_c_host, double obs_tol, int nsteps, double* terms,
                           double* q0_host, double* wsum_host, pph_solve_info* infos, int* steps_done);
 
+/* ---- sources of the transient runs: wells and distributed sources (perphil_amd/csrc/pph_sources.hip) ------------------
+ * no reference counterpart (the reference's dpp_form has no right-hand side beyond the Dirichlet lifting).  With load vectors L_k
+ * (2n values, field-major, constant in time) and rates r_k(t) (q > 0 injects) a theta step solves
+ *   (Sigma M / dt + theta A) d = F (-A_unel p^s + sum_k c[s][k] L_k),   c[s][k] = theta r_k(t_{s+1}) + (1 - theta) r_k(t_s).
+ * F drops what falls on constrained dofs: a well on a Dirichlet node pumps into the boundary condition.
+ *
+ * pph_sources_set* replaces the context's source set: n_dense load vectors [n_dense][2n] (copied into the context) and m point
+ * loads, L[dof] = phi_dof(x_p) on the nodes of the cell that holds x_p in network field[p] (0 or 1) - the transpose of
+ * pph_eval_points: its location rule, tie-breaks and tol; CG-1 and degree 2, all four cell kinds.  A point outside the mesh is
+ * counted in *n_outside and gets an empty row (it stays a source: its coefficient multiplies nothing).  K = n_dense + m sources:
+ * coefficient k < n_dense belongs to dense load k, coefficient n_dense + p to point p.  `field` is a HOST array in both variants;
+ * dense and x are host arrays (pph_sources_set) or device arrays (pph_sources_set_device).  The point rows (m x nodes-per-cell
+ * entries) are formed by one kernel, fetched once (16 bytes per entry) and regrouped on the host by dof (stable: dof first, then
+ * point index) into a CSR that is uploaded (12 bytes per entry, 16 per touched dof): a set-up cost, one sort of those entries.  The set lives on the context, independent of assemblies and of
+ * pph_transient_begin; pph_mesh_build* clears it.  A refused call leaves the set as it was.  pph_sources_count: *count = K, or -1
+ * when the context holds no set.  PPH_ERR_INVALID with a message: no mesh, world != 1, a NULL buffer with a non-zero count (or
+ * n_outside NULL), a negative count, a field index outside {0, 1}, tol outside [0, 0.5), more than 65535 dense loads. */
+int pph_sources_set_device(pph_ctx* ctx, const double* dense_dev /* [n_dense][2n] */, int64_t n_dense,
+                           const double* x_dev /* [m][dim] */, const int32_t* field /* [m], host */, int64_t m, double tol,
+                           int64_t* n_outside);
+int pph_sources_set(pph_ctx* ctx, const double* dense_host, int64_t n_dense, const double* x_host, const int32_t* field, int64_t m,
+                    double tol, int64_t* n_outside);
+int pph_sources_clear(pph_ctx* ctx);
+int pph_sources_count(pph_ctx* ctx, int64_t* count);
+/* b += F sum_k coef[k] L_k for one coefficient row coef [K] (host); b: 2n values, in place.  What the step loop launches per step.
+ * Dense part: one grid-stride pass, every L_k read once, b read and written once (16-byte accesses where b_dev is 16-byte
+ * aligned, 8-byte ones otherwise: same arithmetic, same bits), the sum over k in index order.  Point part: one work item per touched dof walks its CSR row in order.  Either part is skipped when empty.  fp64, no
+ * floating-point atomics: two calls give the same bits, the result does not depend on the grid, host and device variant agree
+ * bit for bit.  PPH_ERR_INVALID with a message: no mesh, world != 1, no source set, a NULL buffer. */
+int pph_sources_apply_device(pph_ctx* ctx, const double* coef /* [K], host */, double* b_dev /* 2n, in/out */);
+int pph_sources_apply(pph_ctx* ctx, const double* coef, double* b_host);
+/* pph_transient_steps_record* with the context's source set: coef [nsteps][K] (host) is uploaded once per call (it shares the
+ * call's one allocation: none and no host-to-device copy per step), and b_s += F sum_k coef[s][k] L_k between the kernel that
+ * forms -F A_unel p^s and the norm of b_s: norms[s][0] is the norm of the full right-hand side, which is also what the zero
+ * right-hand-side shortcut and steady_tol look at.  traj may be NULL (no recording).  Everything else is the contract of
+ * pph_transient_steps.  Also PPH_ERR_INVALID with a message: no source set, or one of another size than K; coef NULL with K > 0. */
+int pph_transient_steps_sources_device(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_dev /* 2n, in/out */, int nsteps,
+                                       double steady_tol, pph_solve_info* infos, double* norms, int* steps_done,
+                                       double* traj_dev /* [nsteps + 1][2n] or NULL */, const double* coef /* [nsteps][K], host */,
+                                       int64_t K);
+int pph_transient_steps_sources(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_host /* 2n, in/out */, int nsteps,
+                                double steady_tol, pph_solve_info* infos, double* norms, int* steps_done, double* traj_host,
+                                const double* coef, int64_t K);
+/* pph_transient_adjoint* with the rate gradients: src_grad [nsteps][K] (host), src_grad[s][k] = w_s^T F L_k, written on the device
+ * per backward step and fetched once at the end, as terms are (rows of steps not reached are 0).  Dense loads: a masked dot
+ * product with per-workgroup partial sums in a fixed order; points: one work item per point over the point rows kept from the
+ * set-up, constrained dofs skipped.  A source enters neither the recursion nor the parameter gradients (it depends neither on
+ * the state nor on the parameters): everything else is the contract of pph_transient_adjoint.  dJ/dr_k(t_j) = theta
+ * src_grad[j-1][k] + (1 - theta) src_grad[j][k], rows outside 0 .. nsteps-1 taken as 0.  Also PPH_ERR_INVALID with a message:
+ * no source set, or one of another size than K; src_grad NULL with K > 0. */
+int pph_transient_adjoint_sources_device(pph_ctx* ctx, const pph_solver_cfg* cfg, const double* traj_dev, const double* g_dev,
+                                         const double* obs_x_dev, int64_t m, const double* obs_c_dev, double obs_tol, int nsteps,
+                                         double* terms, double* q0_dev, double* wsum_dev, pph_solve_info* infos, int* steps_done,
+                                         double* src_grad /* [nsteps][K], host */, int64_t K);
+int pph_transient_adjoint_sources(pph_ctx* ctx, const pph_solver_cfg* cfg, const double* traj_host, const double* g_host,
+                                  const double* obs_x_host, int64_t m, const double* obs_c_host, double obs_tol, int nsteps,
+                                  double* terms, double* q0_host, double* wsum_host, pph_solve_info* infos, int* steps_done,
+                                  double* src_grad, int64_t K);
+
 /* ---- multi-GPU communication hooks -------------------------------------------------------------
  * replaces: PETSc's implicit VecScatter halo exchange and VecDot all-reduce under mpiexec (never run in
  * the reference).  One context per rank holds one cell slab (pph_mesh_build with

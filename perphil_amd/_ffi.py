@@ -51,6 +51,9 @@ EXPORTS = [
     "pph_transient_steps_record", "pph_transient_steps_record_device",
     "pph_transient_bilinear", "pph_transient_bilinear_device", "pph_eval_points_adjoint", "pph_eval_points_adjoint_device",
     "pph_transient_adjoint", "pph_transient_adjoint_device",
+    "pph_sources_set", "pph_sources_set_device", "pph_sources_clear", "pph_sources_count",
+    "pph_sources_apply", "pph_sources_apply_device", "pph_transient_steps_sources", "pph_transient_steps_sources_device",
+    "pph_transient_adjoint_sources", "pph_transient_adjoint_sources_device",
 ]
 
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64)
@@ -234,6 +237,21 @@ def _load() -> C.CDLL:
                                   + [C.c_void_p] * 4 + [C.POINTER(C.c_int)], C.c_int),
         "pph_transient_adjoint_device": ([p, C.POINTER(SolverCfg)] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_double, C.c_int]
                                          + [C.c_void_p] * 4 + [C.POINTER(C.c_int)], C.c_int),
+        "pph_sources_set": ([p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, i64p], C.c_int),
+        "pph_sources_set_device": ([p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, i64p], C.c_int),
+        "pph_sources_clear": ([p], C.c_int),
+        "pph_sources_count": ([p, i64p], C.c_int),
+        "pph_sources_apply": ([p, C.c_void_p, C.c_void_p], C.c_int),
+        "pph_sources_apply_device": ([p, C.c_void_p, C.c_void_p], C.c_int),
+        "pph_transient_steps_sources": ([p, C.POINTER(SolverCfg), C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int64], C.c_int),
+        "pph_transient_steps_sources_device": ([p, C.POINTER(SolverCfg), C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                                C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int64], C.c_int),
+        "pph_transient_adjoint_sources": ([p, C.POINTER(SolverCfg)] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_double, C.c_int]
+                                          + [C.c_void_p] * 4 + [C.POINTER(C.c_int), C.c_void_p, C.c_int64], C.c_int),
+        "pph_transient_adjoint_sources_device": ([p, C.POINTER(SolverCfg)] + [C.c_void_p] * 3
+                                                 + [C.c_int64, C.c_void_p, C.c_double, C.c_int] + [C.c_void_p] * 4
+                                                 + [C.POINTER(C.c_int), C.c_void_p, C.c_int64], C.c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = ABI mismatch: fail loudly
@@ -764,12 +782,16 @@ class Context:
                                             float(dt), int(monolithic)))
 
     def transient_steps(self, cfg: SolverCfg, p, nsteps: int, steady_tol: float = 0.0, raise_on_diverged: bool = True,
-                        record: bool = False):
+                        record: bool = False, coef=None):
         """Advances the mixed field p (2n values, field-major) by up to `nsteps` theta steps IN PLACE: a float64 NumPy array
         (copied in and out) or a device tensor (pph_transient_steps / pph_transient_steps_device).  Returns (steps_done,
         infos [steps_done] of SolveInfo, norms [steps_done, 2] = (||b_s||, ||d_s||)); with ``record`` a fourth entry, the
-        trajectory [steps_done + 1, 2n] of the same kind as p (pph_transient_steps_record*)."""
+        trajectory [steps_done + 1, 2n] of the same kind as p (pph_transient_steps_record*).  ``coef``: None, or the
+        coefficient rows [nsteps, K] of the context's source set (``sources_set``): step s adds F sum_k coef[s, k] L_k to its
+        right-hand side (pph_transient_steps_sources*)."""
         nsteps = int(nsteps)
+        if coef is not None:
+            return self._transient_steps_sources(cfg, p, nsteps, steady_tol, raise_on_diverged, record, coef)
         if record:
             return self._transient_steps_record(cfg, p, nsteps, steady_tol, raise_on_diverged)
         infos = (SolveInfo * max(nsteps, 1))()
@@ -814,6 +836,98 @@ class Context:
         self.last_info = infos[k - 1] if k > 0 else SolveInfo()
         self._check(st, allow_diverged=not raise_on_diverged)
         return k, [infos[i] for i in range(k)], norms[:k].copy(), traj[:k + 1]
+
+    def _transient_steps_sources(self, cfg: SolverCfg, p, nsteps: int, steady_tol: float, raise_on_diverged: bool, record: bool,
+                                 coef):
+        c = np.ascontiguousarray(coef, dtype=np.float64)
+        if c.ndim != 2 or c.shape[0] != nsteps:
+            raise ValueError(f"transient_steps: coef must have shape [{nsteps}, K], got {c.shape}")
+        K = int(c.shape[1])
+        infos = (SolveInfo * max(nsteps, 1))()
+        norms = np.zeros((max(nsteps, 1), 2), dtype=np.float64)
+        done = C.c_int(0)
+        rows = max(nsteps, 0) + 1
+        traj = None
+        if isinstance(p, np.ndarray):
+            if p.dtype != np.float64 or p.shape != (2 * self.n,) or not p.flags.c_contiguous or not p.flags.writeable:
+                raise ValueError(f"transient_steps: p must be a writeable contiguous float64 array of {2 * self.n} values")
+            if record:
+                traj = np.zeros((rows, 2 * self.n), dtype=np.float64)
+            st = lib.pph_transient_steps_sources(self._h, C.byref(cfg), _ptr(p), nsteps, float(steady_tol), infos, _ptr(norms),
+                                                 C.byref(done), _ptr(traj), _ptr(c), K)
+        else:
+            t = self._device_in(p, 2 * self.n, "mixed field")
+            if t.data_ptr() != p.data_ptr():
+                raise ValueError("transient_steps: p must be a contiguous float64 device tensor (it is advanced in place)")
+            if record:
+                traj = self._device_out(rows * 2 * self.n).reshape(rows, 2 * self.n)
+            st = lib.pph_transient_steps_sources_device(self._h, C.byref(cfg), _tptr(t), nsteps, float(steady_tol), infos,
+                                                        _ptr(norms), C.byref(done), None if traj is None else _tptr(traj),
+                                                        _ptr(c), K)
+            self.torch_waits()
+        k = int(done.value)
+        self.last_info = infos[k - 1] if k > 0 else SolveInfo()
+        self._check(st, allow_diverged=not raise_on_diverged)
+        out = (k, [infos[i] for i in range(k)], norms[:k].copy())
+        return out + (traj[:k + 1],) if record else out
+
+    # -- sources of the transient runs (pph_sources.hip) ------------------------------------------------------------------
+    def sources_set(self, dense=None, points=None, fields=None, tol: float = 1e-12) -> int:
+        """Replaces the context's source set (pph_sources_set*): ``dense`` [n_dense, 2n] load vectors (or None), ``points``
+        [m, dim] with the network ``fields`` [m] (0 or 1) of every point (or None).  Arrays, or device tensors for dense and
+        points (both of one kind).  Source k < n_dense is dense load k, source n_dense + p point p.  Returns the number of
+        points outside the mesh (they keep their place in the numbering and load nothing)."""
+        dev = (dense is not None and not isinstance(dense, np.ndarray)) or (points is not None and not isinstance(points, np.ndarray))
+        nd = 0 if dense is None else int(dense.shape[0])
+        m = 0 if points is None else int(points.shape[0])
+        if dense is not None and tuple(dense.shape) != (nd, 2 * self.n):
+            raise ValueError(f"sources_set: dense must have shape [n_dense, {2 * self.n}], got {tuple(dense.shape)}")
+        if points is not None and (len(points.shape) != 2 or points.shape[1] != self.dim):
+            raise ValueError(f"sources_set: points must have shape [m, {self.dim}], got {tuple(points.shape)}")
+        fld = np.zeros(m, dtype=np.int32) if fields is None else np.ascontiguousarray(fields, dtype=np.int32).reshape(-1)
+        if fld.shape != (m,):
+            raise ValueError(f"sources_set: fields must hold one network index per point ({m}), got {fld.shape}")
+        nout = C.c_int64()
+        if dev:
+            if (dense is not None and isinstance(dense, np.ndarray)) or (points is not None and isinstance(points, np.ndarray)):
+                raise ValueError("sources_set: dense and points must be arrays or both device tensors")
+            d = None if nd == 0 else self._device_in(dense.reshape(-1), nd * 2 * self.n, "dense")
+            x = None if m == 0 else self._device_in(points.reshape(-1), m * self.dim, "points")
+            self._check(lib.pph_sources_set_device(self._h, None if d is None else _tptr(d), nd, None if x is None else _tptr(x),
+                                                   _ptr(fld), m, float(tol), C.byref(nout)))
+        else:
+            d = None if nd == 0 else np.ascontiguousarray(dense, dtype=np.float64)
+            x = None if m == 0 else np.ascontiguousarray(points, dtype=np.float64)
+            self._check(lib.pph_sources_set(self._h, _ptr(d), nd, _ptr(x), _ptr(fld), m, float(tol), C.byref(nout)))
+        return int(nout.value)
+
+    def sources_clear(self) -> None:
+        self._check(lib.pph_sources_clear(self._h))
+
+    def sources_count(self) -> int:
+        """Number of sources K of the context's set, -1 without one (pph_sources_count)."""
+        k = C.c_int64()
+        self._check(lib.pph_sources_count(self._h, C.byref(k)))
+        return int(k.value)
+
+    def sources_apply(self, coef, b):
+        """b += F sum_k coef[k] L_k IN PLACE for one coefficient row coef [K]; b: 2n values, a writeable float64 array or a
+        device tensor (pph_sources_apply / pph_sources_apply_device).  Returns b."""
+        c = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1)
+        K = self.sources_count()
+        if K >= 0 and c.shape != (K,):
+            raise ValueError(f"sources_apply: coef must hold {K} values, got {c.shape}")
+        if isinstance(b, np.ndarray):
+            if b.dtype != np.float64 or b.shape != (2 * self.n,) or not b.flags.c_contiguous or not b.flags.writeable:
+                raise ValueError(f"sources_apply: b must be a writeable contiguous float64 array of {2 * self.n} values")
+            self._check(lib.pph_sources_apply(self._h, _ptr(c), _ptr(b)))
+            return b
+        t = self._device_in(b, 2 * self.n, "right-hand side")
+        if t.data_ptr() != b.data_ptr():
+            raise ValueError("sources_apply: b must be a contiguous float64 device tensor (it is added to in place)")
+        self._check(lib.pph_sources_apply_device(self._h, _ptr(c), _tptr(t)))
+        self.torch_waits()
+        return b
 
     # -- transient adjoint (pph_transient_adjoint.hip) ------------------------------------------------------------------
     def transient_bilinear(self, w, p0, p1, theta: float) -> tuple:
@@ -868,10 +982,12 @@ class Context:
         return out, int(nout.value)
 
     def transient_adjoint(self, cfg: SolverCfg, traj, g=None, obs_x=None, obs_c=None, obs_tol: float = 1e-12,
-                          want_wsum: bool = True, raise_on_diverged: bool = True):
+                          want_wsum: bool = True, raise_on_diverged: bool = True, want_src_grad: bool = False):
         """The backward loop over a recorded trajectory traj [N + 1, 2n] (pph_transient_adjoint*): g [N + 1, 2n] and / or the
         observation form obs_x [m, dim], obs_c [N + 1, m, 2]; all arrays or all device tensors.  Returns (terms [N, 5] array,
-        q0, wsum or None, infos [steps_done], steps_done); q0 and wsum are of the kind of traj."""
+        q0, wsum or None, infos [steps_done], steps_done); q0 and wsum are of the kind of traj.  ``want_src_grad``: a sixth
+        entry, src_grad [N, K] array with src_grad[s, k] = w_s^T F L_k for the K sources of the context's set
+        (pph_transient_adjoint_sources*)."""
         dev = not isinstance(traj, np.ndarray)
         n2 = 2 * self.n
         if tuple(traj.shape[1:]) != (n2,) or traj.shape[0] < 2:
@@ -890,28 +1006,37 @@ class Context:
         terms = np.zeros((N, 5), dtype=np.float64)
         infos = (SolveInfo * N)()
         done = C.c_int(0)
+        sg, extra = None, ()
+        if want_src_grad:
+            K = self.sources_count()
+            if K < 0:
+                raise ValueError("transient_adjoint: the context holds no source set (sources_set)")
+            sg = np.zeros((N, K), dtype=np.float64)
+            extra = (_ptr(sg), K)
         if dev:
             flat = lambda v, cnt, name: None if v is None else self._device_in(v.reshape(-1), cnt, name)
             tj, gg = flat(traj, (N + 1) * n2, "traj"), flat(g, (N + 1) * n2, "g")
             ox, oc = flat(obs_x, m * self.dim, "obs_x"), flat(obs_c, (N + 1) * m * 2, "obs_c")
             q0 = self._device_out(n2)
             wsum = self._device_out(n2) if want_wsum else None
-            st = lib.pph_transient_adjoint_device(self._h, C.byref(cfg), _tptr(tj), None if gg is None else _tptr(gg),
-                                                  None if ox is None else _tptr(ox), m, None if oc is None else _tptr(oc),
-                                                  float(obs_tol), N, _ptr(terms), _tptr(q0), None if wsum is None else _tptr(wsum),
-                                                  infos, C.byref(done))
+            fn = lib.pph_transient_adjoint_sources_device if want_src_grad else lib.pph_transient_adjoint_device
+            st = fn(self._h, C.byref(cfg), _tptr(tj), None if gg is None else _tptr(gg), None if ox is None else _tptr(ox), m,
+                    None if oc is None else _tptr(oc), float(obs_tol), N, _ptr(terms), _tptr(q0),
+                    None if wsum is None else _tptr(wsum), infos, C.byref(done), *extra)
             self.torch_waits()
         else:
             arr = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float64)
             tj, gg, ox, oc = arr(traj), arr(g), arr(obs_x), arr(obs_c)
             q0 = np.zeros(n2, dtype=np.float64)
             wsum = np.zeros(n2, dtype=np.float64) if want_wsum else None
-            st = lib.pph_transient_adjoint(self._h, C.byref(cfg), _ptr(tj), _ptr(gg), _ptr(ox), m, _ptr(oc), float(obs_tol), N,
-                                           _ptr(terms), _ptr(q0), _ptr(wsum), infos, C.byref(done))
+            fn = lib.pph_transient_adjoint_sources if want_src_grad else lib.pph_transient_adjoint
+            st = fn(self._h, C.byref(cfg), _ptr(tj), _ptr(gg), _ptr(ox), m, _ptr(oc), float(obs_tol), N, _ptr(terms), _ptr(q0),
+                    _ptr(wsum), infos, C.byref(done), *extra)
         k = int(done.value)
         self.last_info = infos[N - k] if k > 0 else SolveInfo()
         self._check(st, allow_diverged=not raise_on_diverged)
-        return terms, q0, wsum, [infos[s] for s in range(N - k, N)], k
+        out = (terms, q0, wsum, [infos[s] for s in range(N - k, N)], k)
+        return out + (sg,) if want_src_grad else out
 
     # -- export -------------------------------------------------------------------------------
     def csr(self, which: int):

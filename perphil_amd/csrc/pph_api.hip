@@ -181,6 +181,7 @@ int pph_ctx_destroy(pph_ctx* ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   free_system(ctx);
   ctx->mesh.release_all();
+  ctx->src.release();
   for (int f = 0; f < 2; ++f) { ctx->bcmask[f].release(); ctx->g[f].release(); }
   ctx->rownear.release();
   ctx->wmap.release();
@@ -245,6 +246,7 @@ static int mesh_build(pph_ctx* ctx, int dim, int cell_kind, int nx, int ny, int 
   }
   free_system(ctx);
   ctx->mesh.release_all();
+  ctx->src.release();   // (the source set belongs to the mesh it was located on)
   ctx->mesh.km_valid = false;
   ctx->mesh_ok = false;
   ctx->post_u_valid = false;

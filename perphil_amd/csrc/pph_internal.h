@@ -379,6 +379,29 @@ struct IluData {
 };
 void ilu_release(IluData& I);
 
+// Source set of the transient runs (pph_sources.hip): n_dense load vectors and m point loads, K = n_dense + m sources; the
+// coefficient of dense load k is c[k], of point p c[n_dense + p].  The point loads are kept twice: by point (row p: nb dofs and
+// basis values; an outside point: dof -1) for the rate gradients, and regrouped by dof (CSR: row r = touched dof row_dof[r],
+// entries in point order) for the right-hand side.  Follows the mesh: a mesh build clears it.
+struct SourceSet {
+  bool on = false;
+  int64_t n_dense = 0, m = 0, n_touched = 0, n_outside = 0;
+  int nb = 0;                        // basis functions per cell: entries of a by-point row
+  DevBuf<double> dense;              // [n_dense][2n]
+  DevBuf<int64_t> pt_dof;            // [m][nb] dof in 0 .. 2n - 1 (field-major), -1 in the row of an outside point
+  DevBuf<double> pt_w;               // [m][nb]
+  DevBuf<int64_t> rowptr, row_dof;   // [n_touched + 1], [n_touched]
+  DevBuf<int32_t> ent_pt;            // [m * nb] point of an entry
+  DevBuf<double> ent_w;              // [m * nb] its basis value
+  DevBuf<double> coef;               // [K] coefficient row of pph_sources_apply
+  int64_t count() const { return n_dense + m; }
+  void release() {
+    dense.release(); pt_dof.release(); pt_w.release(); rowptr.release(); row_dof.release(); ent_pt.release(); ent_w.release();
+    coef.release();
+    on = false; n_dense = m = n_touched = n_outside = 0; nb = 0;
+  }
+};
+
 struct pph_ctx {
   int device = 0;
   int num_cus = 256;                    // compute units of the device (hipDeviceProp_t::multiProcessorCount)
@@ -424,6 +447,7 @@ struct pph_ctx {
   double tr_b0 = -1.0;                  // ||b_0|| of the run (the first step after pph_transient_begin; < 0: not taken yet)
   uint64_t tr_asm_epoch = 0;
   int tr_bc_epoch = -1;
+  SourceSet src;                        // wells and distributed sources of the transient runs (pph_sources.hip)
   DevBuf<uint8_t> bcmask[2];            // per field: 1 Dirichlet, 2 ghost, 0 free
   DevBuf<double> dinv0[2];              // fused assembly: 1 / diag of A11, A22 ...
   DevBuf<unsigned long long> lam0;      // ... and their spectral bounds (bit patterns), valid when diag0_valid
@@ -860,6 +884,11 @@ int pph_nodal_flux_launch(pph_ctx* ctx, double k1, double k2, double beta, doubl
 int pph_step_lift(pph_ctx* ctx, double sigma1, double sigma2, const double* g1, const double* g2, double* rhs);
 // b = -F A_unel p (pph_transient.hip: the launch behind pph_dpp_step_rhs_device, not waited for); p, b: 2n values
 int pph_step_rhs_launch(pph_ctx* ctx, double k1, double k2, double beta, double mu, const double* p, double* b);
+// sources of the transient runs (pph_sources.hip), enqueued on the context stream.  b += F sum_k coef[k] L_k (coef: K values on
+// the device; b: 2n); out[k] = w^T F L_k (out: K values on the device; part: src_dot_part_count(ctx) doubles of scratch)
+int src_apply_launch(pph_ctx* ctx, const double* coef_dev, double* b);
+int src_dot_launch(pph_ctx* ctx, const double* w, double* part, double* out_dev);
+size_t src_dot_part_count(const pph_ctx* ctx);
 // extreme eigenvalues of a symmetric operator by plain Lanczos (pph_eig.hip; out as pph_extreme_eigenvalues documents it)
 int pph_eig_lanczos(pph_ctx* ctx, const Csr& A, double tol, int max_it, int check_every, double* vec_lo, double* vec_hi,
                     double* out);

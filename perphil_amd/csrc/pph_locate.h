@@ -11,6 +11,7 @@
 // between two boxes (t_e an integer) goes to the upper box, except on the domain's far boundary.
 #pragma once
 #include "pph_internal.h"
+#include "pph_p2.h"
 
 struct EvalGeo { int n[3]; };   // boxes per direction
 
@@ -78,5 +79,46 @@ __device__ static inline int simplex_locate(const double* xi, double* lam, doubl
       }
     }
     return s;
+  }
+}
+
+// basis values N[b] of the box-local point xi (inside, clamped) in its cell; returns the sub-cell.  The values k_eval_points
+// forms, by the same calls in the same order (the transposed evaluation and the point loads of pph_sources.hip).
+template <int KIND, int DEG, int NB>
+__device__ static inline int adj_basis(const double* xi, double* N) {
+  constexpr int DIM = (KIND == PPH_CELL_QUAD || KIND == PPH_CELL_TRI) ? 2 : 3;
+  constexpr bool SIMPLEX = (KIND == PPH_CELL_TRI || KIND == PPH_CELL_TET);
+  if constexpr (!SIMPLEX) {
+    if constexpr (DEG == 1) {
+      double w[3][2];
+#pragma unroll
+      for (int e = 0; e < DIM; ++e) { w[e][0] = 1.0 - xi[e]; w[e][1] = xi[e]; }
+#pragma unroll
+      for (int b = 0; b < NB; ++b) N[b] = q1_shape<DIM>(w, b);
+    } else {
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        double d[3];
+        p2_basis<KIND>(b, xi, &N[b], d);
+      }
+    }
+    return 0;
+  } else {
+    double lam[DIM + 1], D[DIM + 1][3];
+    const int sub = simplex_locate<KIND>(xi, lam, D);
+    if constexpr (DEG == 1) {
+#pragma unroll
+      for (int b = 0; b < NB; ++b) N[b] = lam[b];
+    } else {
+      double xr[DIM];   // reference coordinates of pph_p2.h: xr_j = lam_{j+1}
+#pragma unroll
+      for (int j = 0; j < DIM; ++j) xr[j] = lam[j + 1];
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        double d[3];
+        p2_basis<KIND>(b, xr, &N[b], d);
+      }
+    }
+    return sub;
   }
 }

@@ -316,6 +316,8 @@ extern "C" int pph_dpp_step_rhs(pph_ctx* ctx, double k1, double k2, double beta,
 // with the solve loop of pph_solve_device on whatever path cfg names.  As pph_solve_rhs does per solve, the CONTENTS of the
 // context's right-hand side, lifting and solution are exchanged with saved copies - once per call - and put back on return.
 // Per step the host reads one pair of scalars: ||b_s||^2 and, with it, ||d_{s-1}||^2 that k_step_update left behind.
+// pph_transient_steps_sources*: between the right-hand side and its norm, b_s += F sum_k coef[s][k] L_k with the context's
+// source set (pph_sources.hip); the coefficient rows travel once per call, behind the saved vectors in the call's allocation.
 
 // p = Dirichlet value on the constrained dofs of either field
 __global__ __launch_bounds__(256) void k_step_constrain(double* __restrict__ p, const uint8_t* __restrict__ m0,
@@ -383,9 +385,10 @@ extern "C" int pph_transient_begin(pph_ctx* ctx, double k1, double k2, double be
 }
 
 // the loop between the exchange and the restore; `save`: 3 x 2n doubles, then STEP_MAX_BLOCKS partial sums; `traj`: NULL, or
-// [nsteps + 1][2n] on the device: row 0 receives p after k_step_constrain, row s + 1 after the update of step s
+// [nsteps + 1][2n] on the device: row 0 receives p after k_step_constrain, row s + 1 after the update of step s; `coef`: NULL, or
+// the coefficient rows [nsteps][K] of the context's source set on the device: b_s += F sum_k coef[s][k] L_k (pph_sources.hip)
 static int transient_run(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p, int nsteps, double steady_tol, pph_solve_info* infos,
-                         double* norms, int* steps_done, double* save, double* traj) {
+                         double* norms, int* steps_done, double* save, double* traj, const double* coef, int64_t K) {
   const int64_t n = ctx->n, N = 2 * n;
   const int grid = (int)(ceil_div64(N, 256) < STEP_MAX_BLOCKS ? ceil_div64(N, 256) : STEP_MAX_BLOCKS);
   double* part = save + 3 * N;
@@ -401,6 +404,7 @@ static int transient_run(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p, int
   int s = 0;
   for (; s < nsteps; ++s) {
     PPH_TRY(step_rhs_dev(ctx, ctx->tr_coef[0], ctx->tr_coef[1], ctx->tr_coef[2], ctx->tr_coef[3], p, ctx->rhs.p));
+    if (coef) PPH_TRY(src_apply_launch(ctx, coef + (int64_t)s * K, ctx->rhs.p));
     la_dot(ctx, ctx->rhs.p, ctx->rhs.p, N, 0);
     PPH_TRY(la_fetch(ctx, 0, 2));   // ||b_s||^2 and the ||d_{s-1}||^2 the last update left in slot 1
     const double bn = sqrt(ctx->h_scal[0]);
@@ -432,8 +436,10 @@ static int transient_run(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p, int
   return PPH_OK;
 }
 
+// `sources`: the call is one of pph_transient_steps_sources*: coef_host [nsteps][K] is uploaded once, behind the saved vectors
 static int transient_steps_dev(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_dev, int nsteps, double steady_tol,
-                               pph_solve_info* infos, double* norms, int* steps_done, double* traj) {
+                               pph_solve_info* infos, double* norms, int* steps_done, double* traj, bool sources = false,
+                               const double* coef_host = nullptr, int64_t K = 0) {
   if (steps_done) *steps_done = 0;
   PPH_REQUIRE(ctx, ctx->world == 1, "pph_transient_steps is implemented for single-context meshes");
   PPH_REQUIRE(ctx, ctx->tr_on, "pph_transient_steps before pph_transient_begin");
@@ -442,12 +448,29 @@ static int transient_steps_dev(pph_ctx* ctx, const pph_solver_cfg* cfg, double* 
   PPH_REQUIRE(ctx, ctx->bc_epoch == ctx->tr_bc_epoch, "pph_transient_steps: the Dirichlet sets changed after pph_transient_begin");
   PPH_REQUIRE(ctx, p_dev != nullptr && steps_done != nullptr && cfg != nullptr, "pph_transient_steps: NULL buffer");
   PPH_REQUIRE(ctx, nsteps >= 1, "pph_transient_steps: nsteps must be >= 1, got %d", nsteps);
+  if (sources) {
+    PPH_REQUIRE(ctx, ctx->src.on, "pph_transient_steps_sources: the context holds no source set (pph_sources_set)");
+    PPH_REQUIRE(ctx, ctx->src.count() == K, "pph_transient_steps_sources: coef has %lld columns, the context's source set %lld sources",
+                (long long)K, (long long)ctx->src.count());
+    PPH_REQUIRE(ctx, K == 0 || coef_host != nullptr, "pph_transient_steps_sources: NULL buffer");
+  }
   PPH_TRY(validate_cfg(ctx, cfg));
   PPH_HIP(ctx, hipSetDevice(ctx->device));
   const int64_t N = 2 * ctx->n;
-  DevBuf<double> save;
-  PPH_TRY(save.alloc(ctx, (size_t)(3 * N + STEP_MAX_BLOCKS)));
-  int st = transient_run(ctx, cfg, p_dev, nsteps, steady_tol, infos, norms, steps_done, save.p, traj);
+  const size_t ncoef = sources ? (size_t)nsteps * (size_t)K : 0;
+  DevBuf<double> save;   // the saved vectors, the partial sums, then the coefficient rows: the call's one allocation
+  PPH_TRY(save.alloc(ctx, (size_t)(3 * N + STEP_MAX_BLOCKS) + ncoef));
+  double* coef = sources ? save.p + (size_t)(3 * N + STEP_MAX_BLOCKS) : nullptr;
+  if (ncoef) {
+    const hipError_t ec = hipMemcpyAsync(coef, coef_host, sizeof(double) * ncoef, hipMemcpyHostToDevice, ctx->stream);
+    if (ec != hipSuccess) {
+      (void)hipStreamSynchronize(ctx->stream);
+      save.release();
+      pph_set_error(ctx, "pph_transient_steps_sources: uploading coef failed: %s", hipGetErrorString(ec));
+      return PPH_ERR_HIP;
+    }
+  }
+  int st = transient_run(ctx, cfg, p_dev, nsteps, steady_tol, infos, norms, steps_done, save.p, traj, coef, K);
   const std::string msg = ctx->err;   // (the solve's message survives the clean-up)
   // the context's right-hand side, lifting and solution again hold the bits they held before the call
   la_copy(ctx, ctx->rhs.p, save.p, N);
@@ -481,7 +504,8 @@ extern "C" int pph_transient_steps_record_device(pph_ctx* ctx, const pph_solver_
 
 // the host variants: p (and the trajectory) live on the device for the call
 static int transient_steps_host(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_host, int nsteps, double steady_tol,
-                                pph_solve_info* infos, double* norms, int* steps_done, double* traj_host, bool record) {
+                                pph_solve_info* infos, double* norms, int* steps_done, double* traj_host, bool record,
+                                bool sources = false, const double* coef_host = nullptr, int64_t K = 0) {
   if (steps_done) *steps_done = 0;
   PPH_REQUIRE(ctx, ctx->world == 1, "pph_transient_steps is implemented for single-context meshes");
   PPH_REQUIRE(ctx, ctx->tr_on, "pph_transient_steps before pph_transient_begin");
@@ -496,7 +520,7 @@ static int transient_steps_host(pph_ctx* ctx, const pph_solver_cfg* cfg, double*
   int st = PPH_OK;
   hipError_t e = hipMemcpyAsync(p.p, p_host, sizeof(double) * N, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
-    st = transient_steps_dev(ctx, cfg, p.p, nsteps, steady_tol, infos, norms, steps_done, traj);
+    st = transient_steps_dev(ctx, cfg, p.p, nsteps, steady_tol, infos, norms, steps_done, traj, sources, coef_host, K);
     if (st >= 0 || st == PPH_ERR_DIVERGED) {
       e = hipMemcpyAsync(p_host, p.p, sizeof(double) * N, hipMemcpyDeviceToHost, ctx->stream);
       if (e == hipSuccess && record)
@@ -523,4 +547,21 @@ extern "C" int pph_transient_steps_record(pph_ctx* ctx, const pph_solver_cfg* cf
                                           pph_solve_info* infos, double* norms, int* steps_done, double* traj_host) {
   if (!ctx) return PPH_ERR_INVALID;
   return transient_steps_host(ctx, cfg, p_host, nsteps, steady_tol, infos, norms, steps_done, traj_host, true);
+}
+
+// the same loops with the context's source set (pph_sources.hip): coef [nsteps][K] on the host, traj NULL or as the recording
+// variants take it
+extern "C" int pph_transient_steps_sources_device(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_dev, int nsteps,
+                                                  double steady_tol, pph_solve_info* infos, double* norms, int* steps_done,
+                                                  double* traj_dev, const double* coef, int64_t K) {
+  if (!ctx) return PPH_ERR_INVALID;
+  return transient_steps_dev(ctx, cfg, p_dev, nsteps, steady_tol, infos, norms, steps_done, traj_dev, true, coef, K);
+}
+
+extern "C" int pph_transient_steps_sources(pph_ctx* ctx, const pph_solver_cfg* cfg, double* p_host, int nsteps, double steady_tol,
+                                           pph_solve_info* infos, double* norms, int* steps_done, double* traj_host,
+                                           const double* coef, int64_t K) {
+  if (!ctx) return PPH_ERR_INVALID;
+  return transient_steps_host(ctx, cfg, p_host, nsteps, steady_tol, infos, norms, steps_done, traj_host, traj_host != nullptr, true,
+                              coef, K);
 }

@@ -204,47 +204,7 @@ extern "C" int pph_transient_bilinear(pph_ctx* ctx, const double* w_host, const 
 }
 
 // ---- transposed point evaluation -------------------------------------------------------------------------------------
-// basis values N[b] of the box-local point xi (inside, clamped) in its cell; returns the sub-cell.  The values k_eval_points
-// forms, by the same calls in the same order.
-template <int KIND, int DEG, int NB>
-__device__ static inline int adj_basis(const double* xi, double* N) {
-  constexpr int DIM = (KIND == PPH_CELL_QUAD || KIND == PPH_CELL_TRI) ? 2 : 3;
-  constexpr bool SIMPLEX = (KIND == PPH_CELL_TRI || KIND == PPH_CELL_TET);
-  if constexpr (!SIMPLEX) {
-    if constexpr (DEG == 1) {
-      double w[3][2];
-#pragma unroll
-      for (int e = 0; e < DIM; ++e) { w[e][0] = 1.0 - xi[e]; w[e][1] = xi[e]; }
-#pragma unroll
-      for (int b = 0; b < NB; ++b) N[b] = q1_shape<DIM>(w, b);
-    } else {
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        double d[3];
-        p2_basis<KIND>(b, xi, &N[b], d);
-      }
-    }
-    return 0;
-  } else {
-    double lam[DIM + 1], D[DIM + 1][3];
-    const int sub = simplex_locate<KIND>(xi, lam, D);
-    if constexpr (DEG == 1) {
-#pragma unroll
-      for (int b = 0; b < NB; ++b) N[b] = lam[b];
-    } else {
-      double xr[DIM];   // reference coordinates of pph_p2.h: xr_j = lam_{j+1}
-#pragma unroll
-      for (int j = 0; j < DIM; ++j) xr[j] = lam[j + 1];
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        double d[3];
-        p2_basis<KIND>(b, xr, &N[b], d);
-      }
-    }
-    return sub;
-  }
-}
-
+// (the basis values of a located point: adj_basis, pph_locate.h - shared with pph_sources.hip)
 // out[node * os_node + comp * os_comp] += N_a(x_p) c[p * ncomp + comp] for the nodes a of the cell that holds x_p; ONE workgroup
 // of one wave, points in index order.  *n_outside = number of points outside (written, not added)
 template <int KIND, int DEG>
@@ -414,9 +374,13 @@ struct AdjArgs {
   double *q0, *wsum;
   pph_solve_info* infos;
   int* steps_done;
+  // rate gradients (pph_sources.hip): NULL, or src_grad [nsteps][K] on the device and the scratch of its partial sums
+  double *src_grad = nullptr, *src_part = nullptr;
+  int64_t K = 0;
 };
 
 // the loop between the exchange and the restore.  work: save (3 x 2n) | q | w | b | G | part (5 x BL_MAX_BLOCKS) | terms (5 N)
+// (| the partial sums of the rate gradients | src_grad (N K))
 static int adjoint_run(pph_ctx* ctx, const pph_solver_cfg* cfg, const AdjArgs& a, double* work, unsigned long long* cnt) {
   const int64_t n = ctx->n, N = 2 * n;
   const int grid = (int)(ceil_div64(N, 256) < ADJ_MAX_BLOCKS ? ceil_div64(N, 256) : ADJ_MAX_BLOCKS);
@@ -462,6 +426,7 @@ static int adjoint_run(pph_ctx* ctx, const pph_solver_cfg* cfg, const AdjArgs& a
     if (a.infos) a.infos[s] = info;
     if (st == PPH_ERR_DIVERGED) break;
     PPH_TRY(tb_enqueue(ctx, part, w, a.traj + (int64_t)s * N, a.traj + (int64_t)(s + 1) * N, ctx->tr_theta, terms + 5 * s));
+    if (a.src_grad) PPH_TRY(src_dot_launch(ctx, w, a.src_part, a.src_grad + (int64_t)s * a.K));   // src_grad[s][k] = w_s^T F L_k
     PPH_TRY(pph_step_rhs_launch(ctx, ctx->tr_coef[0], ctx->tr_coef[1], ctx->tr_coef[2], ctx->tr_coef[3], w, b));
     PPH_TRY(functional(s, &Gs));
     hipLaunchKernelGGL(k_adj_update, dim3(grid), dim3(256), 0, ctx->stream, q, Gs, (const double*)b, (const double*)w, a.wsum, m0, m1, n);
@@ -489,21 +454,35 @@ static int adjoint_check(pph_ctx* ctx, const pph_solver_cfg* cfg, const void* tr
   return validate_cfg(ctx, cfg);
 }
 
-extern "C" int pph_transient_adjoint_device(pph_ctx* ctx, const pph_solver_cfg* cfg, const double* traj_dev, const double* g_dev,
-                                            const double* obs_x_dev, int64_t m, const double* obs_c_dev, double obs_tol, int nsteps,
-                                            double* terms, double* q0_dev, double* wsum_dev, pph_solve_info* infos,
-                                            int* steps_done) {
-  if (!ctx) return PPH_ERR_INVALID;
+// the checks of the variants with rate gradients (pph_transient_adjoint_sources*), after adjoint_check
+static int adjoint_sources_check(pph_ctx* ctx, const double* src_grad, int64_t K) {
+  PPH_REQUIRE(ctx, ctx->src.on, "pph_transient_adjoint_sources: the context holds no source set (pph_sources_set)");
+  PPH_REQUIRE(ctx, ctx->src.count() == K, "pph_transient_adjoint_sources: src_grad has %lld columns, the context's source set %lld sources",
+              (long long)K, (long long)ctx->src.count());
+  PPH_REQUIRE(ctx, K == 0 || src_grad != nullptr, "pph_transient_adjoint_sources: NULL buffer");
+  return PPH_OK;
+}
+
+// `sources`: also src_grad [nsteps][K] (host), written on the device per step and fetched once, as terms
+static int adjoint_device(pph_ctx* ctx, const pph_solver_cfg* cfg, const double* traj_dev, const double* g_dev,
+                          const double* obs_x_dev, int64_t m, const double* obs_c_dev, double obs_tol, int nsteps, double* terms,
+                          double* q0_dev, double* wsum_dev, pph_solve_info* infos, int* steps_done, bool sources, double* src_grad,
+                          int64_t K) {
   if (steps_done) *steps_done = 0;
   PPH_TRY(adjoint_check(ctx, cfg, traj_dev, g_dev, obs_x_dev, m, obs_c_dev, obs_tol, nsteps, terms, q0_dev, steps_done));
+  if (sources) PPH_TRY(adjoint_sources_check(ctx, src_grad, K));
   PPH_HIP(ctx, hipSetDevice(ctx->device));
   const int64_t N = 2 * ctx->n;
+  const bool sg = sources && K > 0;
+  const size_t n_base = (size_t)(7 * N) + (size_t)5 * BL_MAX_BLOCKS + (size_t)5 * nsteps;
+  const size_t n_part = sg ? src_dot_part_count(ctx) : 0, n_sg = sg ? (size_t)nsteps * (size_t)K : 0;
   DevBuf<double> work;
   DevBuf<unsigned long long> cnt;
-  PPH_TRY(work.alloc(ctx, (size_t)(7 * N) + (size_t)5 * BL_MAX_BLOCKS + (size_t)5 * nsteps));
+  PPH_TRY(work.alloc(ctx, n_base + n_part + n_sg));
   int st = cnt.alloc(ctx, 1);
   if (st < 0) { work.release(); return st; }
-  const AdjArgs a = {traj_dev, g_dev, obs_x_dev, obs_c_dev, m, obs_tol, nsteps, q0_dev, wsum_dev, infos, steps_done};
+  AdjArgs a = {traj_dev, g_dev, obs_x_dev, obs_c_dev, m, obs_tol, nsteps, q0_dev, wsum_dev, infos, steps_done};
+  if (sg) { a.src_part = work.p + n_base; a.src_grad = a.src_part + n_part; a.K = K; }
   st = adjoint_run(ctx, cfg, a, work.p, cnt.p);
   const std::string msg = ctx->err;   // (the solve's message survives the clean-up)
   // the context's right-hand side, lifting and solution again hold the bits they held before the call
@@ -518,6 +497,12 @@ extern "C" int pph_transient_adjoint_device(pph_ctx* ctx, const pph_solver_cfg* 
     const double* tdev = work.p + 7 * N + (size_t)5 * BL_MAX_BLOCKS + (size_t)5 * (nsteps - done);
     e = hipMemcpyAsync(terms + (size_t)5 * (nsteps - done), tdev, sizeof(double) * 5 * done, hipMemcpyDeviceToHost, ctx->stream);
   }
+  if (sg) {   // ... and the rate gradients of the same steps
+    for (size_t i = 0; i < n_sg; ++i) src_grad[i] = 0.0;
+    if (e == hipSuccess && done > 0 && (st >= 0 || st == PPH_ERR_DIVERGED))
+      e = hipMemcpyAsync(src_grad + (size_t)K * (nsteps - done), a.src_grad + (size_t)K * (nsteps - done),
+                         sizeof(double) * (size_t)K * done, hipMemcpyDeviceToHost, ctx->stream);
+  }
   const hipError_t es = hipStreamSynchronize(ctx->stream);   // (work is freed below; the caller's arrays are free again)
   if (e == hipSuccess) e = es;
   work.release(); cnt.release();
@@ -529,12 +514,31 @@ extern "C" int pph_transient_adjoint_device(pph_ctx* ctx, const pph_solver_cfg* 
   return st;
 }
 
-extern "C" int pph_transient_adjoint(pph_ctx* ctx, const pph_solver_cfg* cfg, const double* traj_host, const double* g_host,
-                                     const double* obs_x_host, int64_t m, const double* obs_c_host, double obs_tol, int nsteps,
-                                     double* terms, double* q0_host, double* wsum_host, pph_solve_info* infos, int* steps_done) {
+extern "C" int pph_transient_adjoint_device(pph_ctx* ctx, const pph_solver_cfg* cfg, const double* traj_dev, const double* g_dev,
+                                            const double* obs_x_dev, int64_t m, const double* obs_c_dev, double obs_tol, int nsteps,
+                                            double* terms, double* q0_dev, double* wsum_dev, pph_solve_info* infos,
+                                            int* steps_done) {
   if (!ctx) return PPH_ERR_INVALID;
+  return adjoint_device(ctx, cfg, traj_dev, g_dev, obs_x_dev, m, obs_c_dev, obs_tol, nsteps, terms, q0_dev, wsum_dev, infos, steps_done,
+                        false, nullptr, 0);
+}
+
+extern "C" int pph_transient_adjoint_sources_device(pph_ctx* ctx, const pph_solver_cfg* cfg, const double* traj_dev,
+                                                    const double* g_dev, const double* obs_x_dev, int64_t m, const double* obs_c_dev,
+                                                    double obs_tol, int nsteps, double* terms, double* q0_dev, double* wsum_dev,
+                                                    pph_solve_info* infos, int* steps_done, double* src_grad, int64_t K) {
+  if (!ctx) return PPH_ERR_INVALID;
+  return adjoint_device(ctx, cfg, traj_dev, g_dev, obs_x_dev, m, obs_c_dev, obs_tol, nsteps, terms, q0_dev, wsum_dev, infos, steps_done,
+                        true, src_grad, K);
+}
+
+static int adjoint_host(pph_ctx* ctx, const pph_solver_cfg* cfg, const double* traj_host, const double* g_host,
+                        const double* obs_x_host, int64_t m, const double* obs_c_host, double obs_tol, int nsteps, double* terms,
+                        double* q0_host, double* wsum_host, pph_solve_info* infos, int* steps_done, bool sources, double* src_grad,
+                        int64_t K) {
   if (steps_done) *steps_done = 0;
   PPH_TRY(adjoint_check(ctx, cfg, traj_host, g_host, obs_x_host, m, obs_c_host, obs_tol, nsteps, terms, q0_host, steps_done));
+  if (sources) PPH_TRY(adjoint_sources_check(ctx, src_grad, K));
   PPH_HIP(ctx, hipSetDevice(ctx->device));
   const size_t N = 2 * (size_t)ctx->n, rows = (size_t)nsteps + 1, dim = (size_t)ctx->mesh.dim;
   const bool obs = obs_c_host != nullptr && m > 0;
@@ -549,9 +553,8 @@ extern "C" int pph_transient_adjoint(pph_ctx* ctx, const pph_solver_cfg* cfg, co
   int st = PPH_OK;
   if (e == hipSuccess) {
     // (an observation form without points is an empty sum: it still counts as given)
-    st = pph_transient_adjoint_device(ctx, cfg, traj, g_host ? g : nullptr, obs ? x : nullptr, obs ? m : 0,
-                                      obs_c_host ? (obs ? c : traj) : nullptr, obs_tol, nsteps, terms, q0, wsum_host ? wsum : nullptr,
-                                      infos, steps_done);
+    st = adjoint_device(ctx, cfg, traj, g_host ? g : nullptr, obs ? x : nullptr, obs ? m : 0, obs_c_host ? (obs ? c : traj) : nullptr,
+                        obs_tol, nsteps, terms, q0, wsum_host ? wsum : nullptr, infos, steps_done, sources, src_grad, K);
     if (st >= 0 || st == PPH_ERR_DIVERGED) {
       e = hipMemcpyAsync(q0_host, q0, sizeof(double) * N, hipMemcpyDeviceToHost, ctx->stream);
       if (e == hipSuccess && wsum_host) e = hipMemcpyAsync(wsum_host, wsum, sizeof(double) * N, hipMemcpyDeviceToHost, ctx->stream);
@@ -565,4 +568,21 @@ extern "C" int pph_transient_adjoint(pph_ctx* ctx, const pph_solver_cfg* cfg, co
     return PPH_ERR_HIP;
   }
   return st;
+}
+
+extern "C" int pph_transient_adjoint(pph_ctx* ctx, const pph_solver_cfg* cfg, const double* traj_host, const double* g_host,
+                                     const double* obs_x_host, int64_t m, const double* obs_c_host, double obs_tol, int nsteps,
+                                     double* terms, double* q0_host, double* wsum_host, pph_solve_info* infos, int* steps_done) {
+  if (!ctx) return PPH_ERR_INVALID;
+  return adjoint_host(ctx, cfg, traj_host, g_host, obs_x_host, m, obs_c_host, obs_tol, nsteps, terms, q0_host, wsum_host, infos,
+                      steps_done, false, nullptr, 0);
+}
+
+extern "C" int pph_transient_adjoint_sources(pph_ctx* ctx, const pph_solver_cfg* cfg, const double* traj_host, const double* g_host,
+                                             const double* obs_x_host, int64_t m, const double* obs_c_host, double obs_tol, int nsteps,
+                                             double* terms, double* q0_host, double* wsum_host, pph_solve_info* infos,
+                                             int* steps_done, double* src_grad, int64_t K) {
+  if (!ctx) return PPH_ERR_INVALID;
+  return adjoint_host(ctx, cfg, traj_host, g_host, obs_x_host, m, obs_c_host, obs_tol, nsteps, terms, q0_host, wsum_host, infos,
+                      steps_done, true, src_grad, K);
 }
